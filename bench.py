@@ -20,7 +20,12 @@ MI355X (~60 GB), so N=1 runs it whole and N>1 strong-scales it over z-slabs.
 metric (BASELINE.json): assembled DOFs/s = active dofs / step time (whole job);
 cut-quadrature points/s and per-phase times are reported beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mesh 512] [--order 4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mesh 512] [--order 4] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds everything else the
+benchmark measures (phase split, per-kernel HIP-event profile and rooflines, configs[1], [3], [4], the 32^3 and
+implicit-structured lines, the moving-domain leg, the scaling projection, the CPU baselines) and writes the full record
+to bench_detail.json.  `--dump-outputs DIR` writes what the last timed step computed (`dump_outputs`).
 """
 from __future__ import annotations
 
@@ -74,12 +79,21 @@ def parse():
     p.add_argument("--mesh", "--n", dest="n", type=int, default=512,
                    help="background mesh n^3 cubes (x6 tets); use --mesh under torchrun (--n is ambiguous there)")
     p.add_argument("--order", type=int, default=4, help="runtime quadrature order (demo_poisson.py:139)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: phase split, per-kernel profile and rooflines, "
+                        "the secondary configurations, the moving-domain leg, the scaling projection and the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (one GPU)")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
     p.add_argument("--cpu-n", type=int, default=256, help="mesh size of the bounded CPU sample (BASELINE.md 3: 256^3)")
-    p.add_argument("--no-secondary", action="store_true", help="skip the configs[1], [3], [4] and implicit-structured lines")
+    p.add_argument("--no-secondary", action="store_true",
+                   help="with --full: skip the configs[1], [3], [4] and implicit-structured lines")
     p.add_argument("--cpu-worker", nargs=4, type=int, metavar=("N", "Z0", "Z1", "ORDER"),
                    help="internal: one process of the all-cores CPU baseline")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def sphere_level_set(torch, n, device):
@@ -143,6 +157,47 @@ class StepResult:
                     nq_volume=system.volume_rules.total_points, nq_interface=system.interface_rules.total_points,
                     n_vol_rules=system.volume_rules.num_rules,
                     n_ghost=0 if system.ghost_facets is None else system.ghost_facets.size)
+
+
+DUMP_SAMPLE = 1 << 20      # entries kept of a dumped array longer than this: a fixed, seeded sample of them
+DUMP_SEED = 1729
+DUMP_COUNTS = ("active_dofs", "nnz", "n_inside", "n_cut", "nq_volume", "nq_interface", "n_vol_rules", "n_ghost")
+
+
+def sample_positions(size, salt):
+    """Sorted positions of the dumped sample of an array of `size` entries: all of them up to DUMP_SAMPLE, otherwise
+    DUMP_SAMPLE positions drawn from the fixed seed (DUMP_SEED, salt) -- the same positions for the same length."""
+    import numpy as np
+    if size <= DUMP_SAMPLE:
+        return np.arange(size, dtype=np.int64)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).integers(0, size, DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(torch, res, b, device, out_dir):
+    """What a caller of the timed path receives from its last step, as .npy files in `out_dir` (float64, the cell
+    classification float32; under 64 MB in all): the CSR matrix (`A_values`, `A_indices`, `A_indptr`), the right-hand
+    side `b`, the cell classification `domain` (-1 inside, 0 cut, +1 outside) and the `inactive_dofs` of the active
+    domain, each sampled at `sample_positions`; `checksums` (sum, sum of |x|, sum of x^2 over the whole of A's values,
+    then of b) and `counts` (DUMP_COUNTS) summarise the step."""
+    import numpy as np
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    indptr, indices, values = res.A.torch_views(device)
+
+    def take(name, t, salt, dtype=np.float64):
+        pos = torch.from_numpy(sample_positions(int(t.numel()), salt)).to(t.device)
+        np.save(out / f"{name}.npy", t[pos].cpu().numpy().astype(dtype))
+
+    take("A_values", values, 1)
+    take("A_indices", indices, 2)
+    take("A_indptr", indptr, 3)
+    take("b", b, 4)
+    take("domain", torch.from_numpy(res.system.cut_data.domain()), 5, np.float32)
+    take("inactive_dofs", torch.from_numpy(res.dom.inactive_dofs), 6)
+    sums = [f(x).item() for x in (values, b) for f in (torch.sum, lambda v: v.abs().sum(), lambda v: (v * v).sum())]
+    np.save(out / "checksums.npy", np.array(sums, dtype=np.float64))
+    counts = res.counts()
+    np.save(out / "counts.npy", np.array([counts[k] for k in DUMP_COUNTS], dtype=np.float64))
 
 
 def cpu_baseline(n, order):
@@ -284,7 +339,10 @@ def kernel_profile(_lib, step, psteps):
     return kernels
 
 
-def measure(n, steps, warmup, order, world, rank, device, profile=True):
+def measure(n, steps, warmup, order, world, rank, device, profile=True, dump_dir=None):
+    """The timed steps of the n^3 workload.  `profile`: also the HIP-event split of the first step, the phase split,
+    the per-kernel profile and the rooflines (extra steps after the timed region); `dump_dir`: write what the last
+    timed step computed (`dump_outputs`, one GPU)."""
     import torch
     import torch.distributed as dist
 
@@ -335,21 +393,23 @@ def measure(n, steps, warmup, order, world, rank, device, profile=True):
     # HIP events (the profile is on for this one step), so the rest of it -- the first allocation of the tables and
     # temporaries from the driver, code-object loading of kernels that run for the first time -- can be told apart
     mem0 = _lib.memory_stats(reset_peak=True)
-    _lib.check(_lib.lib().cfx_profile_enable(1))
-    _lib.check(_lib.lib().cfx_profile_reset())
+    if profile:
+        _lib.check(_lib.lib().cfx_profile_enable(1))
+        _lib.check(_lib.lib().cfx_profile_reset())
     barrier()
     ts = time.perf_counter()
     info = step()
     barrier()
     first_step_ms = 1e3 * (time.perf_counter() - ts)
     first_kernels = {}
-    for i in range(_lib.lib().cfx_profile_count()):
-        name, ms, cnt = C.c_char_p(), C.c_double(), C.c_int64()
-        _lib.check(_lib.lib().cfx_profile_get(i, C.byref(name), C.byref(ms), C.byref(cnt)))
-        if cnt.value:
-            first_kernels[name.value.decode()] = ms.value
-    _lib.check(_lib.lib().cfx_profile_enable(0))
-    _lib.check(_lib.lib().cfx_profile_reset())
+    if profile:
+        for i in range(_lib.lib().cfx_profile_count()):
+            name, ms, cnt = C.c_char_p(), C.c_double(), C.c_int64()
+            _lib.check(_lib.lib().cfx_profile_get(i, C.byref(name), C.byref(ms), C.byref(cnt)))
+            if cnt.value:
+                first_kernels[name.value.decode()] = ms.value
+        _lib.check(_lib.lib().cfx_profile_enable(0))
+        _lib.check(_lib.lib().cfx_profile_reset())
     mem1 = _lib.memory_stats()
     # (the first step sized everything by read-backs; the next one takes its sizes from it and allocates the
     # capacity-sized buffers the timed steps then find in the block cache: it belongs to the setup, like the first)
@@ -370,6 +430,8 @@ def measure(n, steps, warmup, order, world, rank, device, profile=True):
     else:
         last = info
         info = last.counts()
+        if dump_dir is not None:
+            dump_outputs(torch, last, b_buf, device, dump_dir)
     info = {k: v for k, v in info.items() if isinstance(v, (int, float))}
     scale_info = None
     if world > 1:
@@ -421,7 +483,8 @@ def measure(n, steps, warmup, order, world, rank, device, profile=True):
                         steps_to_amortise=(first_step_ms - out["ms_per_step"]) / out["ms_per_step"],
                         split_ms=dict(setup_kernels=round(setup_kernel_ms, 2),
                                       other_kernels_of_the_first_step=round(first_kernel_ms - setup_kernel_ms, 2),
-                                      allocation_module_load_host=round(first_step_ms - first_kernel_ms, 2)),
+                                      allocation_module_load_host=round(first_step_ms - first_kernel_ms, 2))
+                        if profile else None,
                         hbm_allocated_by_first_step_bytes=(mem1["in_use"] + mem1["cached"]) - (mem0["in_use"] + mem0["cached"]),
                         static_table_bytes=static_bytes, static_table_bytes_total=sum(static_bytes.values()),
                         note="mesh-static tables built by the first step and reused by every later one (moving-domain "
@@ -847,6 +910,8 @@ def launcher_command(args, port=None):
         cmd.append("--no-cpu")
     if args.no_secondary:
         cmd.append("--no-secondary")
+    if getattr(args, "full", False):
+        cmd.append("--full")
     return cmd
 
 
@@ -1176,6 +1241,8 @@ def main():
     if args.cpu_worker:
         cpu_slab_worker(*args.cpu_worker)
         return
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("--dump-outputs writes the outputs of a one-GPU step: run it with --gpus 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args))
     import torch
@@ -1223,7 +1290,8 @@ def main():
         measure(8, 1, 0, args.order, 1, 0, device, profile=False)
     torch.cuda.synchronize()
     library_warmup_ms = 1e3 * (time.perf_counter() - tw)
-    m = measure(n, args.steps, args.warmup, args.order, world, rank, device)
+    m = measure(n, args.steps, args.warmup, args.order, world, rank, device, profile=args.full,
+                dump_dir=args.dump_outputs)
     if m.get("setup") is not None:
         m["setup"]["library_warmup_ms"] = library_warmup_ms
     out = {
@@ -1250,6 +1318,13 @@ def main():
               "counts", "step_mode", "multi_gpu", "phases_ms", "setup", "memory", "kernels", "roofline", "roofline_by_kernel", "roofline_longest_kernel",
               "whole_step_roofline"):
         out[k] = m.get(k)
+    if not args.full:
+        # a plain run: the result line and nothing else (no extra legs, no detail file)
+        if rank == 0:
+            print(headline_line(out), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if rank == 0 and world == 1:
         if not args.no_secondary and n != 128:
             s = measure(128, 20, 3, args.order, 1, 0, device, profile=False)

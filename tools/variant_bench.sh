@@ -5,7 +5,7 @@ set -u
 N=$1; K=$2; shift 2
 for L in "$@"; do
   if [ "$L" = "-" ]; then unset CFX_LIB; else export CFX_LIB=$L; fi
-  timeout -k 10 240 python3 bench.py --mesh $N --steps 4 --warmup 1 --no-cpu --no-secondary 2>/dev/null | python3 -c "
+  timeout -k 10 240 python3 bench.py --full --mesh $N --steps 4 --warmup 1 --no-cpu --no-secondary 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 ks = '$K'.split(',')
