@@ -223,6 +223,9 @@ int cfx_apply_lifting_c128(cfx_form_t a, const int8_t* bc_markers, const double*
 {
   CFX_API_BEGIN
   require(a && bc_markers && bc_values && b, CFX_ERR_INVALID_ARGUMENT, "cfx_apply_lifting_c128: null argument");
+  for (const auto& I : a->integrals) // (registered integrands lift through the float64 entry point alone)
+    require(!user_integrand_known(I.kernel), CFX_ERR_INVALID_ARGUMENT,
+            "cfx_apply_lifting_c128: forms with registered integrands take cfx_apply_lifting (float64)");
   require(a->rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_apply_lifting_c128: form is not bilinear");
   const int64_t n = a->V->ndofs * a->V->bs, n1 = a->V1->ndofs * a->V1->bs;
   // b -= sum_k s_k alpha A_k (g - x0): the real lifting kernels on the real and the imaginary part of (g - x0)

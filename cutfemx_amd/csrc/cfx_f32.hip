@@ -268,6 +268,9 @@ int cfx_apply_lifting_f32(cfx_form_t a, const int8_t* bc_markers, const float* b
 {
   CFX_API_BEGIN
   require(a && bc_markers && bc_values && b, CFX_ERR_INVALID_ARGUMENT, "cfx_apply_lifting_f32: null argument");
+  for (const auto& I : a->integrals) // (registered integrands lift through the float64 entry point alone)
+    require(!user_integrand_known(I.kernel), CFX_ERR_INVALID_ARGUMENT,
+            "cfx_apply_lifting_f32: forms with registered integrands take cfx_apply_lifting (float64)");
   const int64_t n = a->V->ndofs * a->V->bs;
   DevArray<double> g = widen(bc_values, n), w0, tmp(n);
   if (x0) w0 = widen(x0, n);

@@ -769,31 +769,122 @@ __global__ void __launch_bounds__(kBlock) scatter_staged_facets_kernel(DevN n_d,
     }
 }
 
-// a cell integral whose integrand was registered at run time: stage 1 through the compiled wrapper, then -- unless the
-// caller wants the staged tensors themselves (A.dump: the row gather, tabulate_entity) -- the scatter above
+// ... of staged tensors of a form between two spaces, [n][nloc0][nloc1] (cells) or [n][2 nloc0][2 nloc1] (interior facets:
+// rows [cell 0, cell 1] of the test dofmap, columns [cell 0, cell 1] of the trial dofmap).  One thread per (entity, test
+// row); `ent` holds the cell ids (stride 1) or the (c0, lf0, c1, lf1) rows (stride 4, facet = 1); bc0 zeroes rows, bc1
+// columns (assemble_cells2_kernel)
+__global__ void __launch_bounds__(kBlock) scatter_staged2_kernel(DevN n_d, const int32_t* __restrict__ ent, int facet,
+                                                                 const int32_t* __restrict__ dofmap0, int nd0, int bs0,
+                                                                 const int32_t* __restrict__ dofmap1, int nd1, int bs1,
+                                                                 const double* __restrict__ staged,
+                                                                 const int8_t* __restrict__ bc0, const int8_t* __restrict__ bc1,
+                                                                 const int64_t* __restrict__ indptr,
+                                                                 const int32_t* __restrict__ indices, double* __restrict__ values,
+                                                                 int* error)
+{
+  const int64_t n = dev_n(n_d);
+  const int ns = facet ? 2 : 1;
+  const int nloc0 = nd0 * bs0, nloc1 = nd1 * bs1, nm0 = ns * nloc0, nm1 = ns * nloc1;
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t e = t / nm0;
+  if (e >= n) return;
+  const int I = (int)(t - e * nm0);
+  const int64_t c[2] = {facet ? ent[4 * e] : ent[e], facet ? ent[4 * e + 2] : 0};
+  const int si = I / nloc0, Ii = I - si * nloc0;
+  const int32_t row = dofmap0[c[si] * nd0 + Ii / bs0] * bs0 + Ii % bs0;
+  const bool row_bc = bc0 && bc0[row];
+  const int64_t rb = indptr[row], re = indptr[row + 1];
+  const double* src = staged + (e * nm0 + I) * nm1;
+  for (int s = 0; s < ns; ++s)
+    for (int j = 0; j < nd1; ++j)
+    {
+      const int32_t col0 = dofmap1[c[s] * nd1 + j] * bs1;
+      const int64_t pos = csr_find(indices, rb, re, col0);
+      if (pos < 0) { *error = 1; continue; }
+      for (int b = 0; b < bs1; ++b)
+      {
+        double v = src[s * nloc1 + j * bs1 + b];
+        if (row_bc || (bc1 && bc1[col0 + b])) v = 0.0;
+        atomicAdd(&values[pos + b], v);
+      }
+    }
+}
+
+// lifting with staged tensors (square or two-space, cells or interior facets; layout as above): row I of the tensor of
+// entity e contracted with alpha (g - x0) over the marked trial columns and subtracted from b (lift_bc_impl,
+// assemble_vector_impl.h:383-436).  A row of an entity without a marked trial dof adds nothing, as in the built-in
+// lifting kernels.
+__global__ void __launch_bounds__(kBlock) lift_staged_kernel(DevN n_d, const int32_t* __restrict__ ent, int facet,
+                                                             const int32_t* __restrict__ dofmap0, int nd0, int bs0,
+                                                             const int32_t* __restrict__ dofmap1, int nd1, int bs1,
+                                                             const double* __restrict__ staged, const int8_t* __restrict__ markers,
+                                                             const double* __restrict__ g, const double* __restrict__ x0,
+                                                             double alpha, double* __restrict__ b)
+{
+  const int64_t n = dev_n(n_d);
+  const int ns = facet ? 2 : 1;
+  const int nloc0 = nd0 * bs0, nloc1 = nd1 * bs1, nm0 = ns * nloc0, nm1 = ns * nloc1;
+  const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t e = t / nm0;
+  if (e >= n) return;
+  const int I = (int)(t - e * nm0);
+  const int64_t c[2] = {facet ? ent[4 * e] : ent[e], facet ? ent[4 * e + 2] : 0};
+  const double* src = staged + (e * nm0 + I) * nm1;
+  double sum = 0.0;
+  bool any = false;
+  for (int s = 0; s < ns; ++s)
+    for (int j = 0; j < nd1; ++j)
+    {
+      const int32_t col0 = dofmap1[c[s] * nd1 + j] * bs1;
+      for (int k = 0; k < bs1; ++k)
+        if (markers[col0 + k])
+        {
+          sum += src[s * nloc1 + j * bs1 + k] * alpha * (g[col0 + k] - (x0 ? x0[col0 + k] : 0.0));
+          any = true;
+        }
+    }
+  if (!any) return;
+  const int si = I / nloc0, Ii = I - si * nloc0;
+  const int32_t row = dofmap0[c[si] * nd0 + Ii / bs0] * bs0 + Ii % bs0;
+  atomicAdd(&b[row], -sum);
+}
+
+// an integral whose integrand was registered at run time (square or two-space form): stage 1 through the compiled
+// wrapper, then -- unless the caller wants the staged tensors themselves (A.dump: the row gather, tabulate_entity) --
+// the scatter above, or the lifting contraction (A.lift_markers).  Buffers are sized from the capacities; the launches
+// take their lengths from the counts (sync-free steps).
 void launch_user_integral(const cfx_form_s* a, const cfx_integral_dev& I, AsmArgs A, int64_t only_index, int use_rule, int parts)
 {
   const cfx_space_s* V = a->V;
-  require(A.lift_markers == nullptr, CFX_ERR_INVALID_ARGUMENT, "apply_lifting is not available for user integrands");
+  const cfx_space_s* V1 = a->V1 ? a->V1 : a->V;
+  const bool rect = a->rectangular();
   const bool single = only_index >= 0;
-  const int nd = V->ndofs_cell, bs = V->bs;
+  const int nd = V->ndofs_cell, bs = V->bs, nd1 = V1->ndofs_cell, bs1 = V1->bs;
+  require(A.lift_markers == nullptr || a->rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_apply_lifting: form is not bilinear");
   if (I.type == CFX_INTERIOR_FACET)
   {
-    // macro tensors [facet][2 nloc][2 nloc]: to the caller (row gather, tabulate_entity), or staged and scattered
+    // macro tensors [facet][2 nloc0][2 nloc1]: to the caller (row gather, tabulate_entity), or staged and scattered
     const DevN n = single ? DevN(1) : I.n_entities.devn();
     if (n.cap == 0) return;
     if (A.dump) { user_stage1_facets(a, I, A.dump, only_index); return; }
-    const int64_t nm = 2 * (int64_t)nd * bs;
-    DevArray<double> staged(n.cap * nm * nm);
+    const int64_t nm0 = 2 * (int64_t)nd * bs, nm1 = 2 * (int64_t)nd1 * bs1;
+    DevArray<double> staged(n.cap * nm0 * nm1);
     user_stage1_facets(a, I, staged.p, only_index);
-    launch("scatter_staged", scatter_staged_facets_kernel, grid_for(n.cap * nm), dim3(kBlock), 0, n,
-           I.entities.p + 4 * (single ? only_index : 0), V->dofmap.p, nd, bs, (const double*)staged.p, A.bc0, A.bc1, A.indptr,
-           A.indices, A.values, A.error);
+    const int32_t* rows = I.entities.p + 4 * (single ? only_index : 0);
+    if (A.lift_markers)
+      launch("lift_staged", lift_staged_kernel, grid_for(n.cap * nm0), dim3(kBlock), 0, n, rows, 1, V->dofmap.p, nd, bs,
+             V1->dofmap.p, nd1, bs1, (const double*)staged.p, A.lift_markers, A.lift_values, A.lift_x0, A.lift_alpha, A.values);
+    else if (rect)
+      launch("scatter_staged2", scatter_staged2_kernel, grid_for(n.cap * nm0), dim3(kBlock), 0, n, rows, 1, V->dofmap.p, nd, bs,
+             V1->dofmap.p, nd1, bs1, (const double*)staged.p, A.bc0, A.bc1, A.indptr, A.indices, A.values, A.error);
+    else
+      launch("scatter_staged", scatter_staged_facets_kernel, grid_for(n.cap * nm0), dim3(kBlock), 0, n, rows, V->dofmap.p, nd, bs,
+             (const double*)staged.p, A.bc0, A.bc1, A.indptr, A.indices, A.values, A.error);
     return;
   }
   require(I.type == CFX_CELL, CFX_ERR_INVALID_ARGUMENT, "user integrands are cell or interior-facet integrals");
-  const int64_t nloc = (int64_t)nd * bs;
-  const int64_t nt = a->rank == 2 ? nloc * nloc : nloc;
+  const int64_t nloc = (int64_t)nd * bs, nloc1 = (int64_t)nd1 * bs1;
+  const int64_t nt = a->rank == 2 ? nloc * nloc1 : nloc;
   for (int part = 1; part <= 2; ++part)
   {
     if (!(parts & part)) continue;
@@ -805,9 +896,16 @@ void launch_user_integral(const cfx_form_s* a, const cfx_integral_dev& I, AsmArg
     if (A.dump) { user_stage1(a, I, runtime, A.dump, 0, 0, only_index); continue; }
     DevArray<double> staged(n.cap * nt);
     user_stage1(a, I, runtime, staged.p, 0, 0, only_index);
-    const int32_t* cells = runtime ? I.rules->parent_map.p : I.entities.p;
-    launch("scatter_staged", scatter_staged_kernel, grid_for(n.cap * nloc), dim3(kBlock), 0, n, cells + (single ? only_index : 0),
-           V->dofmap.p, nd, bs, a->rank, (const double*)staged.p, A.bc0, A.bc1, A.indptr, A.indices, A.values, A.error);
+    const int32_t* cells = (runtime ? I.rules->parent_map.p : I.entities.p) + (single ? only_index : 0);
+    if (A.lift_markers)
+      launch("lift_staged", lift_staged_kernel, grid_for(n.cap * nloc), dim3(kBlock), 0, n, cells, 0, V->dofmap.p, nd, bs,
+             V1->dofmap.p, nd1, bs1, (const double*)staged.p, A.lift_markers, A.lift_values, A.lift_x0, A.lift_alpha, A.values);
+    else if (rect)
+      launch("scatter_staged2", scatter_staged2_kernel, grid_for(n.cap * nloc), dim3(kBlock), 0, n, cells, 0, V->dofmap.p, nd, bs,
+             V1->dofmap.p, nd1, bs1, (const double*)staged.p, A.bc0, A.bc1, A.indptr, A.indices, A.values, A.error);
+    else
+      launch("scatter_staged", scatter_staged_kernel, grid_for(n.cap * nloc), dim3(kBlock), 0, n, cells, V->dofmap.p, nd, bs,
+             a->rank, (const double*)staged.p, A.bc0, A.bc1, A.indptr, A.indices, A.values, A.error);
   }
 }
 
@@ -1134,6 +1232,7 @@ __global__ void __launch_bounds__(kBlock) assemble_facets2_kernel(AsmArgs A, Rec
 // every integral of a rectangular form, or one entity of one of them (only_index >= 0)
 void launch_rectangular(const cfx_form_s* a, const cfx_integral_dev& I, AsmArgs A, int64_t only_index = -1, int use_rule = 0)
 {
+  if (user_integrand_known(I.kernel)) { launch_user_integral(a, I, A, only_index, use_rule, 3); return; }
   const cfx_space_s* V0 = a->V;
   const cfx_space_s* V1 = a->V1;
   RectArgs R{V1->dofmap.p, V0->degree, V0->bs, V0->ndofs_cell, V1->degree, V1->bs, V1->ndofs_cell};
@@ -1706,7 +1805,9 @@ void dump_integral(cfx_form_s* a, int integral, int parts, double* out, bool fol
   A.x = V->mesh->x.p; A.conn = V->mesh->conn.p; A.dofmap = V->dofmap.p;
   A.dump = out; A.error = err.p;
   A.dump_fold = fold_facets ? 1 : 0;
-  launch_integral(a, a->integrals[integral], A, -1, 0, parts);
+  const cfx_integral_dev& I = a->integrals[integral];
+  if (a->rectangular() && user_integrand_known(I.kernel)) launch_user_integral(a, I, A, -1, 0, parts); // [n][NDB0][NDB1]
+  else launch_integral(a, I, A, -1, 0, parts);
 }
 // stage 1 of the P1 gradient-jump facets for the row gather: 10 doubles per facet (facet_jump_p1_kernel)
 void dump_facet_jumps_p1(cfx_form_s* a, int integral, double* out, int* error)
@@ -1834,11 +1935,31 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
     require(bilinear == (rank == 2), CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: kernel rank does not match the form");
     require(in.qdegree >= 0 && in.qdegree <= CFX_QUAD_MAX_DEGREE, CFX_ERR_INVALID_ARGUMENT,
             "cfx_form_create: quadrature degree out of range");
+    if (user)
+    {
+      // a square form takes integrands registered for one space, a form between two spaces those of
+      // cfx_integrand_register2 (the tensor shapes differ)
+      if (rect)
+        require(user_integrand_two(in.kernel), CFX_ERR_INVALID_ARGUMENT,
+                "cfx_form_create2: the integrand was registered for a square form (one space); a form between two spaces "
+                "takes an integrand registered with cfx_integrand_register2");
+      else
+        require(!user_integrand_two(in.kernel), CFX_ERR_INVALID_ARGUMENT,
+                "cfx_form_create: the integrand was registered with cfx_integrand_register2 for a form between two spaces; "
+                "a square form takes one registered for one space");
+    }
     if (in.type == CFX_INTERIOR_FACET && user)
-      require(user_integrand_kind(in.kernel) == 1 && !rect && V->degree <= 2 && in.rules == nullptr && 2 * V->ndofs_cell * V->bs <= 24,
+    {
+      require(user_integrand_kind(in.kernel) == 1 && V->degree <= 2 && V1->degree <= 2 && 2 * V->ndofs_cell * V->bs <= 24
+                  && 2 * V1->ndofs_cell * V1->bs <= 24,
               CFX_ERR_INVALID_ARGUMENT,
               "cfx_form_create: an interior-facet integral takes an integrand registered with cfx_integrand_register_facet "
-              "(standard facets, spaces of degree 1 or 2 with at most 24 macro dofs)");
+              "(or cfx_integrand_register2 with facet = 1): spaces of degree 1 or 2 with at most 24 macro dofs on each side");
+      if (in.rules)
+        require(in.rules->host_width == 4 && in.point_data == nullptr, CFX_ERR_INVALID_ARGUMENT,
+                "cfx_form_create: runtime rules of an interior-facet integral are facet-hosted rules over interior rows "
+                "(cfx_cut_create_facets with row_width 4)");
+    }
     else if (in.type == CFX_INTERIOR_FACET)
     {
       require(in.kernel == CFX_K_GHOST_GRADJUMP || in.kernel == CFX_K_EXTENSION_L2 || in.kernel == CFX_K_JUMP
@@ -1857,7 +1978,8 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
                   "cfx_form_create: a cell integral takes cell-hosted rules (pass facet-hosted rules through "
                   "cfx_facet_rules_to_cells)");
     else if (user)
-      require(in.type == CFX_CELL && !rect && V->degree <= 2 && user_integrand_kind(in.kernel) == 0, CFX_ERR_INVALID_ARGUMENT,
+      require(in.type == CFX_CELL && V->degree <= 2 && V1->degree <= 2 && user_integrand_kind(in.kernel) == 0,
+              CFX_ERR_INVALID_ARGUMENT,
               "cfx_form_create: a cell integral takes an integrand registered with cfx_integrand_register (spaces of degree 1 or 2)");
     else
       require(in.kernel == CFX_K_MASS || in.kernel == CFX_K_STIFFNESS || in.kernel == CFX_K_NITSCHE
@@ -1866,7 +1988,13 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
               CFX_ERR_INVALID_ARGUMENT,
               "cfx_form_create: unknown cell kernel id (the divergence blocks need different test and trial spaces: "
               "cfx_form_create2)");
-    if (rect)
+    if (rect && user)
+    {
+      // registered integrands between two spaces: cell integrals over standard cells and / or runtime rules (with
+      // per-point data), interior facets over standard facets and / or facet-hosted rules; a coefficient is packed with
+      // the TEST space's dofmap
+    }
+    else if (rect)
     {
       // test space != trial space: cell integrals of the kernels assemble_cells2_kernel knows, shapes that match
       require(in.coefficient == nullptr && in.point_data == nullptr, CFX_ERR_INVALID_ARGUMENT,
@@ -1904,7 +2032,7 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
       // a scalar coefficient of the form's element multiplies the integrand (kappa grad u . grad v, rho u v, the
       // density-weighted elasticity of python/demo/demo_compliance_optimization.py)
       require(in.coefficient == nullptr || in.kernel == CFX_K_MASS || in.kernel == CFX_K_STIFFNESS
-                  || in.kernel == CFX_K_ELASTICITY,
+                  || in.kernel == CFX_K_ELASTICITY || (rect && user),
               CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: a coefficient is accepted by the mass, stiffness and elasticity terms");
       if (in.coefficient) I.coefficient = to_device(in.coefficient, V->ndofs);
     }

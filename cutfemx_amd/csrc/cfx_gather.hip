@@ -4584,6 +4584,11 @@ struct Rect2Slot
   const int32_t* rule_keys;
   const int32_t* rule_first;
   unsigned rule_mask;
+  // a registered integrand: its staged tensors [entity][nd0 bs0][nd1 bs1] -- standard cells through the cell -> entity
+  // map st_index (-1: not in the list), runtime rules by rule index -- instead of a built-in kernel (st_index != null)
+  const int32_t* st_index;
+  const double* st_std;
+  const double* st_rule;
 };
 struct Rect2Args
 {
@@ -4605,6 +4610,14 @@ struct Rect2Args
   int n_slots;
   Rect2Slot slot[4];
 };
+
+// cell -> position in an entity list (the staged tensors of a registered integrand)
+__global__ void stage_index_kernel(DevN n_d, const int32_t* __restrict__ cells, int32_t* __restrict__ index)
+{
+  const int64_t n = dev_n(n_d);
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n) index[cells[e]] = (int32_t)e;
+}
 
 template <int TDIM, bool ORDERED>
 __global__ void __launch_bounds__(kWave) assemble_rows2_kernel(Rect2Args A)
@@ -4650,9 +4663,29 @@ __global__ void __launch_bounds__(kWave) assemble_rows2_kernel(Rect2Args A)
       Geo<TDIM> g;
       load_cell<TDIM>(A.x, A.conn, c, g);
       jacobian<TDIM>(g);
+      const int nloc0 = R.nd0 * R.bs0, nloc1 = R.nd1 * R.bs1, I0 = ia * R.bs0 + ik;
+      auto add_staged = [&](const double* src) {
+#pragma unroll
+        for (int j = 0; j < MAXND; ++j)
+#pragma unroll
+          for (int b = 0; b < MAXBS; ++b)
+            if (j < R.nd1 && b < R.bs1) acc[j][b] += src[j * R.bs1 + b];
+      };
       for (int s = 0; s < A.n_slots; ++s)
       {
         const Rect2Slot& S = A.slot[s];
+        if (S.st_index)
+        {
+          if (mark & S.std_bit)
+          {
+            const int32_t k = S.st_index[c];
+            if (k >= 0) add_staged(S.st_std + ((int64_t)k * nloc0 + I0) * nloc1);
+          }
+          if (mark & S.rule_bit)
+            for (int64_t e = first_rule(S.rule_keys, S.rule_first, S.rule_mask, (int32_t)c); e < dev_len(S.nr) && S.parent_map[e] == c; ++e)
+              add_staged(S.st_rule + (e * nloc0 + I0) * nloc1);
+          continue;
+        }
         if (mark & S.std_bit)
         {
           int npts;
@@ -4734,6 +4767,12 @@ bool assemble_rect_rows(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, cons
   cfx_row_plan& plan = row_plan(a);
   if (!plan.usable || plan.n_cell_slots > 4) return false;
   if (plan.n_active_rows.cap() == 0) return true;
+  // registered integrands: stage 1 writes their local tensors (standard cells, runtime rules), the gather reads them --
+  // one writer per row as for the built-in kernels (bitwise reproducible with CFX_DETERMINISTIC=1).  Buffers are sized
+  // from the capacities; the cell -> entity map covers the cells of the (possibly pending) list.
+  std::vector<DevArray<double>> staged;
+  std::vector<DevArray<int32_t>> index;
+  const int64_t nt = (int64_t)V0->ndofs_cell * V0->bs * V1->ndofs_cell * V1->bs;
   const Adjacency& adj = V0->dof_cells();
   Rect2Args A{};
   A.n_active = plan.n_active_rows; A.active_rows = plan.active_rows.p;
@@ -4756,6 +4795,25 @@ bool assemble_rect_rows(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, cons
       S.offsets = I.rules->offsets.p; S.parent_map = I.rules->parent_map.p;
       S.points = I.rules->points.p; S.weights = I.rules->weights.p;
       S.rule_keys = plan.rule_keys[s].p; S.rule_first = plan.rule_first[s].p; S.rule_mask = plan.rule_mask[s];
+    }
+    if (user_integrand_known(I.kernel))
+    {
+      const int ii = plan.cell_slot_integral[s];
+      staged.emplace_back(std::max<int64_t>(I.n_entities.cap(), 1) * nt);
+      S.st_std = staged.back().p;
+      if (I.n_entities.cap() > 0) dump_integral(a, ii, 1, staged.back().p);
+      index.emplace_back(std::max<int64_t>(V0->mesh->ncells, 1));
+      S.st_index = index.back().p;
+      dev_fill(index.back().p, 0xff, sizeof(int32_t) * (size_t)V0->mesh->ncells);
+      if (I.n_entities.cap() > 0)
+        launch("rect_stage_index", stage_index_kernel, grid_for(I.n_entities.cap()), dim3(kBlock), 0, I.n_entities.devn(),
+               I.entities.p, index.back().p);
+      if (S.rule_bit)
+      {
+        staged.emplace_back(I.rules->nr.cap() * nt);
+        S.st_rule = staged.back().p;
+        dump_integral(a, ii, 2, staged.back().p);
+      }
     }
   }
   const int64_t nrows_cap = A.n_active.cap * V0->bs;

@@ -130,6 +130,7 @@ __device__ inline void cfx_tabulate_p2(const double* X, double* N, double (*dN)[
     for (int t = 0; t < CFX_TDIM; ++t) dN[CFX_TDIM + 1 + e][t] = 4.0 * (lam[ea[e]] * g[eb[e]][t] + g[ea[e]][t] * lam[eb[e]]);
   }
 }
+#ifdef CFX_ND
 // the basis of the form's space: CFX_ND dofs per cell
 __device__ inline void cfx_tabulate(const double* X, double* N, double (*dN)[CFX_TDIM])
 {
@@ -139,6 +140,25 @@ __device__ inline void cfx_tabulate(const double* X, double* N, double (*dN)[CFX
   cfx_tabulate_p2(X, N, dN);
 #endif
 }
+#else
+// two-space variants: the basis of the test space (CFX_ND0 dofs per cell) and of the trial space (CFX_ND1)
+__device__ inline void cfx_tabulate0(const double* X, double* N, double (*dN)[CFX_TDIM])
+{
+#if CFX_ND0 == CFX_TDIM + 1
+  cfx_tabulate_p1(X, N, dN);
+#else
+  cfx_tabulate_p2(X, N, dN);
+#endif
+}
+__device__ inline void cfx_tabulate1(const double* X, double* N, double (*dN)[CFX_TDIM])
+{
+#if CFX_ND1 == CFX_TDIM + 1
+  cfx_tabulate_p1(X, N, dN);
+#else
+  cfx_tabulate_p2(X, N, dN);
+#endif
+}
+#endif
 // K[t][d] = d xi_t / d x_d and det J of the affine cell with vertices coordinate_dofs[(CFX_TDIM + 1)][3]
 __device__ inline double cfx_inverse_jacobian(const double* xc, double (*K)[CFX_TDIM])
 {
@@ -181,7 +201,9 @@ __device__ inline double cfx_cell_diameter(const double* xc)
 }
 )RTC";
 
-// the wrapper: CFX_USER_FN is the registered function
+// the wrapper: CFX_USER_FN is the registered function.  CFXW_ND (dofs per cell of the test space: the coefficient's
+// packing), CFXW_NR (rows: local dimension of the test space) and CFXW_NC (columns: of the trial space) are defined by
+// the engine -- CFX_ND, CFX_NDB, CFX_NDB for a square form, CFX_ND0, CFX_NDB0, CFX_NDB1 for a two-space one
 const char* kWrapper = R"RTC(
 #define CFX_MAXQ 64
 extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1(RtcArgs A)
@@ -197,15 +219,15 @@ extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1(RtcArgs A)
     const cfx_i64 node = A.conn[cell * (CFX_TDIM + 1) + v];
     for (int d = 0; d < 3; ++d) xc[3 * v + d] = A.x[3 * node + d];
   }
-  // packed coefficient: [ND][coeff_bs] (a scalar Function for bilinear forms, a Function of the form's space -- CFX_BS
-  // components per dof -- for linear forms on vector spaces)
-  double w[CFX_NDB];
+  // packed coefficient: [ND][coeff_bs] (a scalar Function of the test space's dofmap for bilinear forms, a Function of
+  // the form's space -- CFX_BS components per dof -- for linear forms on vector spaces)
+  double w[CFXW_NR];
   if (A.coeff)
-    for (int j = 0; j < CFX_ND; ++j)
-      for (int b = 0; b < A.coeff_bs; ++b) w[j * A.coeff_bs + b] = A.coeff[(cfx_i64)A.dofmap[cell * CFX_ND + j] * A.coeff_bs + b];
-  const int NT = A.rank == 2 ? CFX_NDB * CFX_NDB : CFX_NDB;
-  double T[CFX_NDB * CFX_NDB];
-  for (int i = 0; i < CFX_NDB * CFX_NDB; ++i) T[i] = 0.0;
+    for (int j = 0; j < CFXW_ND; ++j)
+      for (int b = 0; b < A.coeff_bs; ++b) w[j * A.coeff_bs + b] = A.coeff[(cfx_i64)A.dofmap[cell * CFXW_ND + j] * A.coeff_bs + b];
+  const int NT = A.rank == 2 ? CFXW_NR * CFXW_NC : CFXW_NR;
+  double T[CFXW_NR * CFXW_NC];
+  for (int i = 0; i < CFXW_NR * CFXW_NC; ++i) T[i] = 0.0;
   if (A.runtime)
   {
     const int q0 = A.offsets[e], nq = A.offsets[e + 1] - q0;
@@ -233,7 +255,11 @@ extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1(RtcArgs A)
 
 // the facet wrapper: one thread per (c0, lf0, c1, lf1) row.  The points: the reference facet rule pushed to physical
 // space from cell 0's facet lf0 (its vertices in ascending local order) and pulled back to both reference cells -- what
-// the built-in facet kernels do (cfx_elem.h: facet_local_row) -- with the facet's measure in the weights.
+// the built-in facet kernels do (cfx_elem.h: facet_local_row) -- with the facet's measure in the weights.  Entities
+// f >= n_std of an integral with facet-hosted rules integrate over rule f - n_std instead (assemble_facets_kernel with
+// RT = true): its points live on the simplex of the host vertices, its weights are used as stored, and the pulled-back
+// points go to `scratch` (two [nq capacity][TDIM] arrays at the rule's own offsets) -- a rule of any length, no
+// truncation.  Macro tensor [2 CFXW_NR][2 CFXW_NC]: rows [cell 0, cell 1] of the test space, columns of the trial space.
 struct RtcFacetArgs
 {
   const double* x;
@@ -248,6 +274,13 @@ struct RtcFacetArgs
   double params[8];
   const double* coeff;
   double* out;
+  int64_t n_std, f0; // facet-hosted rules: entity f0 + f of the integral is rule f0 + f - n_std when >= n_std
+  const int32_t* offsets;
+  const double* rpoints;
+  const double* rweights;
+  const int32_t* host_verts;
+  double* scratch;
+  int64_t scratch_stride; // doubles per side in `scratch` (nq capacity * TDIM)
 };
 const char* kFacetWrapper = R"RTC(
 struct RtcFacetArgs
@@ -260,9 +293,16 @@ struct RtcFacetArgs
   double params[8];
   const double* coeff;
   double* out;
+  cfx_i64 n_std, f0;
+  const cfx_i32* offsets; const double* rpoints; const double* rweights; const cfx_i32* host_verts;
+  double* scratch;
+  cfx_i64 scratch_stride;
 };
 #define CFX_MAXQF 32
-extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1(RtcFacetArgs A)
+// RT: the launch covers facet-hosted rules (cfx_user_stage1_rules); the standard facets' entry point is compiled
+// without that code (as assemble_facets_kernel<..., RT>), so its registers are those of a standard-facet kernel
+template <bool RT>
+__device__ __forceinline__ void cfx_facet_stage(const RtcFacetArgs& A)
 {
   const cfx_i64 f = (cfx_i64)blockIdx.x * 256 + threadIdx.x;
   cfx_i64 n = A.n_cap;
@@ -277,15 +317,23 @@ extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1(RtcFacetArgs A
       const cfx_i64 node = A.conn[(s ? c1 : c0) * (CFX_TDIM + 1) + v];
       for (int d = 0; d < 3; ++d) xc[(s * (CFX_TDIM + 1) + v) * 3 + d] = A.x[3 * node + d];
     }
-  double w[2 * CFX_ND];
+  double w[2 * CFXW_ND];
   if (A.coeff)
     for (int s = 0; s < 2; ++s)
-      for (int j = 0; j < CFX_ND; ++j) w[s * CFX_ND + j] = A.coeff[A.dofmap[(s ? c1 : c0) * CFX_ND + j]];
+      for (int j = 0; j < CFXW_ND; ++j) w[s * CFXW_ND + j] = A.coeff[A.dofmap[(s ? c1 : c0) * CFXW_ND + j]];
   double K0[CFX_TDIM][CFX_TDIM], K1[CFX_TDIM][CFX_TDIM];
   (void)cfx_inverse_jacobian(xc, K0);
   (void)cfx_inverse_jacobian(xc + (CFX_TDIM + 1) * 3, K1);
-  // the facet's vertices: those of cell 0 except lf0, ascending local index
+  const cfx_i64 r = RT ? A.f0 + f - A.n_std : -1; // >= 0: a facet-hosted rule
+  // the facet's vertices: those of cell 0 except lf0, ascending local index (a facet-hosted rule: its host vertices)
   double xf[CFX_TDIM][3];
+  if (RT)
+    for (int j = 0; j < CFX_TDIM; ++j)
+    {
+      const cfx_i64 v = A.host_verts[r * CFX_TDIM + j];
+      for (int d = 0; d < 3; ++d) xf[j][d] = A.x[3 * v + d];
+    }
+  else
   {
     int k = 0;
     for (int i = 0; i <= CFX_TDIM; ++i)
@@ -309,36 +357,53 @@ extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1(RtcFacetArgs A
     measure = sqrt(cx * cx + cy * cy + cz * cz);
   }
 #endif
-  const int nq = A.nref < CFX_MAXQF ? A.nref : CFX_MAXQF;
-  double P0[CFX_MAXQF * CFX_TDIM], P1[CFX_MAXQF * CFX_TDIM], wq[CFX_MAXQF];
-  for (int q = 0; q < nq; ++q)
-  {
-    double l0 = 1.0, xq[CFX_TDIM];
-    for (int t = 0; t < CFX_TDIM - 1; ++t) l0 -= A.ref_points[q * (CFX_TDIM - 1) + t];
-    for (int d = 0; d < CFX_TDIM; ++d)
+  // the points fp[nq][TDIM - 1] on the simplex xf, pushed to physical space and pulled back to both cells
+  auto pull_back = [&](const double* fp, int nq, double* P0, double* P1) {
+    for (int q = 0; q < nq; ++q)
     {
-      double v = l0 * xf[0][d];
-      for (int t = 0; t < CFX_TDIM - 1; ++t) v += A.ref_points[q * (CFX_TDIM - 1) + t] * xf[t + 1][d];
-      xq[d] = v;
-    }
-    for (int t = 0; t < CFX_TDIM; ++t)
-    {
-      double a = 0.0, b = 0.0;
+      double l0 = 1.0, xq[CFX_TDIM];
+      for (int t = 0; t < CFX_TDIM - 1; ++t) l0 -= fp[q * (CFX_TDIM - 1) + t];
       for (int d = 0; d < CFX_TDIM; ++d)
       {
-        a += K0[t][d] * (xq[d] - xc[d]);
-        b += K1[t][d] * (xq[d] - xc[(CFX_TDIM + 1) * 3 + d]);
+        double v = l0 * xf[0][d];
+        for (int t = 0; t < CFX_TDIM - 1; ++t) v += fp[q * (CFX_TDIM - 1) + t] * xf[t + 1][d];
+        xq[d] = v;
       }
-      P0[q * CFX_TDIM + t] = a;
-      P1[q * CFX_TDIM + t] = b;
+      for (int t = 0; t < CFX_TDIM; ++t)
+      {
+        double a = 0.0, b = 0.0;
+        for (int d = 0; d < CFX_TDIM; ++d)
+        {
+          a += K0[t][d] * (xq[d] - xc[d]);
+          b += K1[t][d] * (xq[d] - xc[(CFX_TDIM + 1) * 3 + d]);
+        }
+        P0[q * CFX_TDIM + t] = a;
+        P1[q * CFX_TDIM + t] = b;
+      }
     }
-    wq[q] = A.ref_weights[q] * measure;
+  };
+  double T[4 * CFXW_NR * CFXW_NC];
+  for (int i = 0; i < 4 * CFXW_NR * CFXW_NC; ++i) T[i] = 0.0;
+  if constexpr (RT)
+  {
+    const int q0 = A.offsets[r], nq = A.offsets[r + 1] - q0;
+    double* P0 = A.scratch + (cfx_i64)q0 * CFX_TDIM;
+    double* P1 = A.scratch + A.scratch_stride + (cfx_i64)q0 * CFX_TDIM;
+    pull_back(A.rpoints + (cfx_i64)q0 * (CFX_TDIM - 1), nq, P0, P1);
+    CFX_USER_FN(T, A.coeff ? w : (const double*)0, A.params, xc, eli, nq, P0, P1, A.rweights + q0);
   }
-  double T[4 * CFX_NDB * CFX_NDB];
-  for (int i = 0; i < 4 * CFX_NDB * CFX_NDB; ++i) T[i] = 0.0;
-  CFX_USER_FN(T, A.coeff ? w : (const double*)0, A.params, xc, eli, nq, P0, P1, wq);
-  for (int i = 0; i < 4 * CFX_NDB * CFX_NDB; ++i) A.out[f * (4 * CFX_NDB * CFX_NDB) + i] = T[i];
+  else
+  {
+    const int nq = A.nref < CFX_MAXQF ? A.nref : CFX_MAXQF;
+    double P0[CFX_MAXQF * CFX_TDIM], P1[CFX_MAXQF * CFX_TDIM], wq[CFX_MAXQF];
+    pull_back(A.ref_points, nq, P0, P1);
+    for (int q = 0; q < nq; ++q) wq[q] = A.ref_weights[q] * measure;
+    CFX_USER_FN(T, A.coeff ? w : (const double*)0, A.params, xc, eli, nq, P0, P1, wq);
+  }
+  for (int i = 0; i < 4 * CFXW_NR * CFXW_NC; ++i) A.out[f * (4 * CFXW_NR * CFXW_NC) + i] = T[i];
 }
+extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1(RtcFacetArgs A) { cfx_facet_stage<false>(A); }
+extern "C" __global__ void __launch_bounds__(256) cfx_user_stage1_rules(RtcFacetArgs A) { cfx_facet_stage<true>(A); }
 )RTC";
 
 // hipRTC through dlopen: the engine does not link it (a process that never registers an integrand never loads it,
@@ -385,9 +450,18 @@ struct UserIntegrand
   std::string name, source;
   int rank = 2;
   int kind = 0;                              // 0: cell integrand, 1: interior-facet integrand
-  std::map<int, std::vector<char>> code;     // (tdim * 100 + nd) * 10 + bs -> code object for gfx950
-  std::map<int, hipModule_t> module;
-  std::map<int, hipFunction_t> function;
+  bool two = false;                          // a bilinear integrand between two spaces (cfx_integrand_register2)
+  std::map<int64_t, std::vector<char>> code; // variant key (variant_key) -> code object for gfx950
+  std::map<int64_t, hipModule_t> module;
+  std::map<int64_t, hipFunction_t> function;
+};
+
+// (tdim, dofs per cell, block size) of the form's space; nd1 > 0: (tdim, nd0, bs0) of the test space, (nd1, bs1) of the
+// trial space of a two-space integrand
+struct Variant
+{
+  int tdim, nd0, bs0, nd1 = 0, bs1 = 0;
+  int64_t key() const { return ((((int64_t)tdim * 100 + nd0) * 10 + bs0) * 100 + nd1) * 10 + bs1; }
 };
 
 std::vector<UserIntegrand>& integrands()
@@ -404,15 +478,27 @@ std::mutex& rtc_mutex()
   return m;
 }
 
-const std::vector<char>& compiled(UserIntegrand& u, int tdim, int nd, int bs = 1)
+std::string variant_defines(const Variant& v)
 {
-  const int key = (tdim * 100 + nd) * 10 + bs;
+  auto def = [](const char* k, const std::string& val) { return std::string("#define ") + k + " " + val + "\n"; };
+  std::string d = def("CFX_TDIM", std::to_string(v.tdim));
+  if (v.nd1 == 0)
+    d += def("CFX_ND", std::to_string(v.nd0)) + def("CFX_BS", std::to_string(v.bs0)) + def("CFX_NDB", "(CFX_ND * CFX_BS)")
+         + def("CFXW_ND", "CFX_ND") + def("CFXW_NR", "CFX_NDB") + def("CFXW_NC", "CFX_NDB");
+  else
+    d += def("CFX_ND0", std::to_string(v.nd0)) + def("CFX_BS0", std::to_string(v.bs0)) + def("CFX_NDB0", "(CFX_ND0 * CFX_BS0)")
+         + def("CFX_ND1", std::to_string(v.nd1)) + def("CFX_BS1", std::to_string(v.bs1)) + def("CFX_NDB1", "(CFX_ND1 * CFX_BS1)")
+         + def("CFXW_ND", "CFX_ND0") + def("CFXW_NR", "CFX_NDB0") + def("CFXW_NC", "CFX_NDB1");
+  return d;
+}
+
+const std::vector<char>& compiled(UserIntegrand& u, const Variant& v)
+{
+  const int64_t key = v.key();
   auto it = u.code.find(key);
   if (it != u.code.end()) return it->second;
   Rtc& r = rtc();
-  const std::string src = std::string("#define CFX_TDIM ") + std::to_string(tdim) + "\n#define CFX_ND " + std::to_string(nd)
-                          + "\n#define CFX_BS " + std::to_string(bs) + "\n#define CFX_NDB (CFX_ND * CFX_BS)"
-                          + "\n#define CFX_USER_FN " + u.name + "\n" + kPrelude + "\n" + u.source + "\n"
+  const std::string src = variant_defines(v) + "#define CFX_USER_FN " + u.name + "\n" + kPrelude + "\n" + u.source + "\n"
                           + (u.kind == 1 ? kFacetWrapper : kWrapper);
   hiprtcProgram prog = nullptr;
   if (r.create(&prog, src.c_str(), (u.name + ".hip").c_str(), 0, nullptr, nullptr) != HIPRTC_SUCCESS)
@@ -436,19 +522,38 @@ const std::vector<char>& compiled(UserIntegrand& u, int tdim, int nd, int bs = 1
   return u.code.emplace(key, std::move(code)).first->second;
 }
 
-hipFunction_t function_of(UserIntegrand& u, int tdim, int nd, int bs = 1)
+hipFunction_t function_of(UserIntegrand& u, const Variant& v, bool rules = false)
 {
-  const int key = (tdim * 100 + nd) * 10 + bs;
-  auto it = u.function.find(key);
+  const int64_t key = v.key(), fkey = 2 * key + (rules ? 1 : 0);
+  auto it = u.function.find(fkey);
   if (it != u.function.end()) return it->second;
-  const std::vector<char>& code = compiled(u, tdim, nd, bs);
-  hipModule_t mod = nullptr;
-  CFX_HIP(hipModuleLoadData(&mod, code.data()));
+  auto mt = u.module.find(key);
+  hipModule_t mod = mt != u.module.end() ? mt->second : nullptr;
+  if (!mod)
+  {
+    const std::vector<char>& code = compiled(u, v);
+    CFX_HIP(hipModuleLoadData(&mod, code.data()));
+    u.module[key] = mod;
+  }
   hipFunction_t fn = nullptr;
-  CFX_HIP(hipModuleGetFunction(&fn, mod, "cfx_user_stage1"));
-  u.module[key] = mod;
-  u.function[key] = fn;
+  CFX_HIP(hipModuleGetFunction(&fn, mod, rules ? "cfx_user_stage1_rules" : "cfx_user_stage1"));
+  u.function[fkey] = fn;
   return fn;
+}
+
+// the variant a form asks of integrand u: its space, or (test, trial) when they differ; the integrand must have been
+// registered for that kind of form
+Variant form_variant(const cfx_form_s* a, const UserIntegrand& u)
+{
+  const cfx_space_s* V = a->V;
+  const bool rect = a->rectangular();
+  require(u.two == rect, CFX_ERR_INVALID_ARGUMENT,
+          rect ? "user integrand: a form between two spaces takes an integrand registered with cfx_integrand_register2"
+               : "user integrand: an integrand registered with cfx_integrand_register2 serves forms between two spaces "
+                 "(cfx_form_create2)");
+  Variant v{V->mesh->tdim, V->ndofs_cell, V->bs};
+  if (rect) { v.nd1 = a->V1->ndofs_cell; v.bs1 = a->V1->bs; }
+  return v;
 }
 
 // reference rule of (dim, degree) in HBM for the wrapper (the engine's own kernels read the tables from their module)
@@ -506,6 +611,12 @@ int user_integrand_rank(int kernel)
   require(user_integrand_known_locked(kernel), CFX_ERR_INVALID_ARGUMENT, "unknown user integrand id");
   return integrands()[kernel - CFX_K_USER_BASE].rank;
 }
+bool user_integrand_two(int kernel)
+{
+  std::lock_guard<std::mutex> lock(rtc_mutex());
+  require(user_integrand_known_locked(kernel), CFX_ERR_INVALID_ARGUMENT, "unknown user integrand id");
+  return integrands()[kernel - CFX_K_USER_BASE].two;
+}
 int user_integrand_kind(int kernel)
 {
   std::lock_guard<std::mutex> lock(rtc_mutex());
@@ -514,19 +625,21 @@ int user_integrand_kind(int kernel)
 }
 
 // stage 1 of a user integrand over the standard entities (runtime = false) or the runtime rules of integral I of form a:
-// local tensors into `out` (out_mode / out_stride: see RtcArgs); `first` / `count` >= 0 restrict the launch to one entity
+// local tensors into `out` (out_mode / out_stride: see RtcArgs); `first` / `count` >= 0 restrict the launch to one entity.
+// A form between two spaces stages [NDB0][NDB1] tensors (rows: test space, columns: trial space).
 void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, double* out, int out_mode, int64_t out_stride,
                  int64_t only_index)
 {
   std::lock_guard<std::mutex> lock(rtc_mutex());
   const cfx_space_s* V = a->V;
   require(user_integrand_known_locked(I.kernel), CFX_ERR_INVALID_ARGUMENT, "unknown user integrand id");
-  require((V->degree == 1 || V->degree == 2) && I.type == CFX_CELL && !a->rectangular(), CFX_ERR_INVALID_ARGUMENT,
-          "user integrands serve cell integrals of Lagrange spaces of degree 1 or 2");
+  require((V->degree == 1 || V->degree == 2) && (a->V1->degree == 1 || a->V1->degree == 2) && I.type == CFX_CELL,
+          CFX_ERR_INVALID_ARGUMENT, "user integrands serve cell integrals of Lagrange spaces of degree 1 or 2");
   UserIntegrand& u = integrands()[I.kernel - CFX_K_USER_BASE];
   require(u.kind == 0, CFX_ERR_INVALID_ARGUMENT, "this user integrand was registered for interior-facet integrals");
-  require(V->ndofs_cell * V->bs <= 30, CFX_ERR_INVALID_ARGUMENT, "user integrands: at most 30 local dofs");
-  const int tdim = V->mesh->tdim, nd = V->ndofs_cell;
+  const Variant var = form_variant(a, u);
+  require(V->ndofs_cell * V->bs <= 30 && a->V1->ndofs_cell * a->V1->bs <= 30, CFX_ERR_INVALID_ARGUMENT,
+          "user integrands: at most 30 local dofs");
   RtcArgs A{};
   A.x = V->mesh->x.p; A.conn = V->mesh->conn.p; A.dofmap = V->dofmap.p;
   A.rank = a->rank; A.runtime = runtime ? 1 : 0;
@@ -547,7 +660,7 @@ void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, d
   }
   else
   {
-    RuleCopy& rc = reference_rule(tdim, I.qdegree);
+    RuleCopy& rc = reference_rule(var.tdim, I.qdegree);
     require(rc.n <= 64, CFX_ERR_INVALID_ARGUMENT, "user integrand: the standard rule has more than 64 points");
     A.ref_points = rc.points.p; A.ref_weights = rc.weights.p; A.nref = rc.n;
     A.entities = I.entities.p + (only_index >= 0 ? only_index : 0);
@@ -555,59 +668,104 @@ void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, d
   }
   A.n_cap = n.cap; A.n_dev = n.dev;
   if (n.cap == 0) return;
-  module_launch(function_of(u, tdim, nd, V->bs), n.cap, &A);
+  module_launch(function_of(u, var), n.cap, &A);
 }
 
 // stage 1 of a user interior-facet integrand over the (c0, lf0, c1, lf1) rows of integral I: macro tensors
-// [facet][2 NDB][2 NDB] into `out` (the layout the row gather and the scatter read); only_index >= 0: one facet
+// [facet][2 NDB0][2 NDB1] into `out` (the layout the row gather and the scatters read); only_index >= 0: one facet.
+// Entities past the standard facets integrate over the integral's facet-hosted rules.
 void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* out, int64_t only_index)
 {
   std::lock_guard<std::mutex> lock(rtc_mutex());
   const cfx_space_s* V = a->V;
+  const cfx_space_s* V1 = a->V1;
   require(user_integrand_known_locked(I.kernel), CFX_ERR_INVALID_ARGUMENT, "unknown user integrand id");
   UserIntegrand& u = integrands()[I.kernel - CFX_K_USER_BASE];
   require(u.kind == 1 && I.type == CFX_INTERIOR_FACET, CFX_ERR_INVALID_ARGUMENT,
           "this user integrand was registered for cell integrals (cfx_integrand_register_facet registers facet integrands)");
-  require((V->degree == 1 || V->degree == 2) && !a->rectangular() && a->rank == 2 && I.rules == nullptr, CFX_ERR_INVALID_ARGUMENT,
-          "user facet integrands serve bilinear forms on Lagrange spaces of degree 1 or 2 over standard facets");
-  const int tdim = V->mesh->tdim, nd = V->ndofs_cell;
-  require(2 * nd * V->bs <= 24, CFX_ERR_INVALID_ARGUMENT,
+  require((V->degree == 1 || V->degree == 2) && (V1->degree == 1 || V1->degree == 2) && a->rank == 2, CFX_ERR_INVALID_ARGUMENT,
+          "user facet integrands serve bilinear forms on Lagrange spaces of degree 1 or 2");
+  const Variant var = form_variant(a, u);
+  require(2 * V->ndofs_cell * V->bs <= 24 && 2 * V1->ndofs_cell * V1->bs <= 24, CFX_ERR_INVALID_ARGUMENT,
           "user facet integrands: at most 24 macro dofs (scalar spaces of degree 1 or 2, vector spaces of degree 1)");
   RtcFacetArgs A{};
   A.x = V->mesh->x.p; A.conn = V->mesh->conn.p; A.dofmap = V->dofmap.p;
   for (int k = 0; k < 8; ++k) A.params[k] = I.params[k];
   A.coeff = I.coefficient.n > 0 ? I.coefficient.p : nullptr;
-  RuleCopy& rc = reference_rule(tdim - 1, I.qdegree);
+  RuleCopy& rc = reference_rule(var.tdim - 1, I.qdegree);
   require(rc.n <= 32, CFX_ERR_INVALID_ARGUMENT, "user facet integrand: the facet rule has more than 32 points");
   A.ref_points = rc.points.p; A.ref_weights = rc.weights.p; A.nref = rc.n;
-  A.rows = I.entities.p + 4 * (only_index >= 0 ? only_index : 0);
-  A.out = out;
-  const DevN n = only_index >= 0 ? DevN(1) : I.n_entities.devn();
-  A.n_cap = n.cap; A.n_dev = n.dev;
-  if (n.cap == 0) return;
-  module_launch(function_of(u, tdim, nd, V->bs), n.cap, &A);
+  hipFunction_t fn_std = function_of(u, var, false);
+  if (!(I.rules && I.n_std >= 0))
+  {
+    // standard facets only: the whole list, whose length may still be in HBM
+    A.rows = I.entities.p + 4 * (only_index >= 0 ? only_index : 0);
+    A.out = out;
+    A.f0 = only_index >= 0 ? only_index : 0;
+    A.n_std = INT64_MAX;
+    const DevN n = only_index >= 0 ? DevN(1) : I.n_entities.devn();
+    A.n_cap = n.cap; A.n_dev = n.dev;
+    if (n.cap > 0) module_launch(fn_std, n.cap, &A);
+    return;
+  }
+  // [standard facets, facet-hosted rules] (exact lengths: form creation refuses a pending list next to the rules); the
+  // rules' entry point gets the pulled-back points of every rule point in two [points][TDIM] arrays indexed by the rules'
+  // own offsets -- a rule of any length, no truncation
+  const int64_t lo = only_index >= 0 ? only_index : 0, hi = only_index >= 0 ? only_index + 1 : I.n_entities.value();
+  const int64_t mid = std::min(std::max(I.n_std, lo), hi);
+  const int64_t nt = 4 * (int64_t)V->ndofs_cell * V->bs * V1->ndofs_cell * V1->bs;
+  A.n_std = I.n_std;
+  if (mid > lo)
+  {
+    A.rows = I.entities.p + 4 * lo; A.out = out; A.f0 = lo;
+    A.n_cap = mid - lo; A.n_dev = nullptr;
+    module_launch(fn_std, A.n_cap, &A);
+  }
+  if (hi > mid)
+  {
+    const int64_t nq = std::max<int64_t>(I.rules->nq.key(), 1);
+    DevArray<double> scratch(2 * nq * var.tdim);
+    A.offsets = I.rules->offsets.p; A.rpoints = I.rules->points.p; A.rweights = I.rules->weights.p;
+    A.host_verts = I.rules->host_verts.p;
+    A.scratch = scratch.p; A.scratch_stride = nq * var.tdim;
+    A.rows = I.entities.p + 4 * mid; A.out = out + (mid - lo) * nt; A.f0 = mid;
+    A.n_cap = hi - mid; A.n_dev = nullptr;
+    module_launch(function_of(u, var, true), A.n_cap, &A);
+  }
 }
 } // namespace cfx
 
 extern "C" {
 
-static int register_integrand(const char* name, const char* source, int rank, int kind, int tdim, int nd, int bs, int* kernel_id)
+static int register_integrand(const char* name, const char* source, int rank, int kind, int tdim, int nd, int bs, int nd1,
+                              int bs1, int* kernel_id)
 {
   CFX_API_BEGIN
-  require(name && source && kernel_id, CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_register: null argument");
+  const char* fn = nd1 > 0 ? "cfx_integrand_register2" : "cfx_integrand_register";
+  require(name && source && kernel_id, CFX_ERR_INVALID_ARGUMENT, (std::string(fn) + ": null argument").c_str());
   require(rank == 1 || rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_register: rank must be 1 or 2");
   require(kind == 0 || rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_register_facet: interior-facet integrands are bilinear");
   for (const char* p = name; *p; ++p)
     require((*p >= 'a' && *p <= 'z') || (*p >= 'A' && *p <= 'Z') || *p == '_' || (p != name && *p >= '0' && *p <= '9'),
-            CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_register: the name must be a C identifier");
+            CFX_ERR_INVALID_ARGUMENT, (std::string(fn) + ": the name must be a C identifier").c_str());
+  auto lagrange = [&](int n, int b) { return (n == tdim + 1 || n == (tdim + 1) * (tdim + 2) / 2) && b >= 1 && b <= 3; };
   require((tdim == 2 || tdim == 3) && nd >= tdim + 1 && nd <= 10 && bs >= 1 && bs <= 3, CFX_ERR_INVALID_ARGUMENT,
-          "cfx_integrand_register: variant to validate: tdim 2 or 3, dofs per cell of a degree-1 or degree-2 space, block size 1..3");
+          (std::string(fn) + ": variant to validate: tdim 2 or 3, dofs per cell of a degree-1 or degree-2 space, block size 1..3").c_str());
+  if (nd1 != 0)
+  {
+    require(lagrange(nd, bs) && lagrange(nd1, bs1), CFX_ERR_INVALID_ARGUMENT,
+            "cfx_integrand_register2: variant (tdim, nd0, bs0, nd1, bs1): tdim 2 or 3, dofs per cell of a degree-1 or "
+            "degree-2 space (tdim + 1 or (tdim + 1)(tdim + 2) / 2) and block size 1..3 for both spaces");
+    require(kind == 0 || (2 * nd * bs <= 24 && 2 * nd1 * bs1 <= 24), CFX_ERR_INVALID_ARGUMENT,
+            "cfx_integrand_register2: interior-facet integrands take at most 24 macro dofs on each side");
+  }
   std::lock_guard<std::mutex> lock(rtc_mutex());
   UserIntegrand u;
-  u.name = name; u.source = source; u.rank = rank; u.kind = kind;
+  u.name = name; u.source = source; u.rank = rank; u.kind = kind; u.two = nd1 != 0;
   // compiled here for ONE variant so that a source that does not compile is refused at registration (no GPU needed:
-  // hipRTC targets gfx950 explicitly); the other (tdim, dofs per cell, block size) variants are compiled on first use
-  (void)compiled(u, tdim, nd, bs);
+  // hipRTC targets gfx950 explicitly); the other variants are compiled on first use
+  Variant v{tdim, nd, bs, nd1, bs1};
+  (void)compiled(u, v);
   integrands().push_back(std::move(u));
   *kernel_id = CFX_K_USER_BASE + (int)integrands().size() - 1;
   CFX_API_END
@@ -615,18 +773,25 @@ static int register_integrand(const char* name, const char* source, int rank, in
 
 int cfx_integrand_register(const char* name, const char* source, int rank, int* kernel_id)
 {
-  return register_integrand(name, source, rank, 0, 3, 4, 1, kernel_id);
+  return register_integrand(name, source, rank, 0, 3, 4, 1, 0, 0, kernel_id);
 }
 
 int cfx_integrand_register_facet(const char* name, const char* source, int* kernel_id)
 {
-  return register_integrand(name, source, 2, 1, 3, 4, 1, kernel_id);
+  return register_integrand(name, source, 2, 1, 3, 4, 1, 0, 0, kernel_id);
 }
 
 int cfx_integrand_register_variant(const char* name, const char* source, int rank, int facet, int tdim, int ndofs_cell, int bs,
                                    int* kernel_id)
 {
-  return register_integrand(name, source, rank, facet ? 1 : 0, tdim, ndofs_cell, bs, kernel_id);
+  return register_integrand(name, source, rank, facet ? 1 : 0, tdim, ndofs_cell, bs, 0, 0, kernel_id);
+}
+
+int cfx_integrand_register2(const char* name, const char* source, int facet, int tdim, int nd0, int bs0, int nd1, int bs1,
+                            int* kernel_id)
+{
+  // (nd1 <= 0 is no trial space: refused by the variant check as a two-space variant)
+  return register_integrand(name, source, 2, facet ? 1 : 0, tdim, nd0, bs0, nd1 > 0 ? nd1 : -1, bs1, kernel_id);
 }
 
 int cfx_integrand_compile(int kernel_id, int tdim, int ndofs_cell)
@@ -641,7 +806,26 @@ int cfx_integrand_compile_bs(int kernel_id, int tdim, int ndofs_cell, int bs)
   require(user_integrand_known_locked(kernel_id), CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_compile: unknown id");
   require((tdim == 2 || tdim == 3) && ndofs_cell >= tdim + 1 && ndofs_cell <= 10 && bs >= 1 && bs <= 3, CFX_ERR_INVALID_ARGUMENT,
           "cfx_integrand_compile: tdim 2 or 3, dofs per cell of a degree-1 or degree-2 space, block size 1..3");
-  (void)compiled(integrands()[kernel_id - CFX_K_USER_BASE], tdim, ndofs_cell, bs);
+  UserIntegrand& u = integrands()[kernel_id - CFX_K_USER_BASE];
+  require(!u.two, CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_compile: a two-space integrand compiles with cfx_integrand_compile2");
+  (void)compiled(u, Variant{tdim, ndofs_cell, bs});
+  CFX_API_END
+}
+
+int cfx_integrand_compile2(int kernel_id, int tdim, int nd0, int bs0, int nd1, int bs1)
+{
+  CFX_API_BEGIN
+  std::lock_guard<std::mutex> lock(rtc_mutex());
+  require(user_integrand_known_locked(kernel_id), CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_compile2: unknown id");
+  UserIntegrand& u = integrands()[kernel_id - CFX_K_USER_BASE];
+  require(u.two, CFX_ERR_INVALID_ARGUMENT,
+          "cfx_integrand_compile2: the integrand was registered for square forms (cfx_integrand_compile_bs)");
+  auto lagrange = [&](int n, int b) { return (n == tdim + 1 || n == (tdim + 1) * (tdim + 2) / 2) && b >= 1 && b <= 3; };
+  require((tdim == 2 || tdim == 3) && lagrange(nd0, bs0) && lagrange(nd1, bs1), CFX_ERR_INVALID_ARGUMENT,
+          "cfx_integrand_compile2: tdim 2 or 3, dofs per cell of a degree-1 or degree-2 space, block size 1..3");
+  require(u.kind == 0 || (2 * nd0 * bs0 <= 24 && 2 * nd1 * bs1 <= 24), CFX_ERR_INVALID_ARGUMENT,
+          "cfx_integrand_compile2: interior-facet integrands take at most 24 macro dofs on each side");
+  (void)compiled(u, Variant{tdim, nd0, bs0, nd1, bs1});
   CFX_API_END
 }
 

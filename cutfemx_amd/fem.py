@@ -163,6 +163,14 @@ class CutForm:
             raise TypeError("Integral.scale belongs to complex forms (fold a real constant into `params`)")
         self._h_im = None
 
+        if self.trial_space is not V:
+            # a registered two-space integrand packs its coefficient with the TEST space's dofmap
+            for i in self.integrals:
+                cs = getattr(i.coefficient, "function_space", None)
+                if i.kernel in _user_integrand_two and cs is not None and cs is not V:
+                    raise ValueError("cfx_form_create2: the coefficient of a registered two-space integrand must be a "
+                                     "Function of the test space (it is packed with the test space's dofmap)")
+
         def create(part):
             # (the arrays an Integral hands over live until its next _cstruct call: each form is created -- and its host
             # arrays uploaded -- before the next one is described)
@@ -237,9 +245,10 @@ class overlap:
 
 
 _user_integrand_rank: dict[int, int] = {}
+_user_integrand_two: set[int] = set()   # ids of cfx_integrand_register2
 
 
-def register_integrand(name: str, source: str, rank: int = 2, facet: bool = False, variant=None) -> int:
+def register_integrand(name: str, source: str, rank: int = 2, facet: bool = False, variant=None, trial=None) -> int:
     """Register the HIP C++ source of an integrand; returns the id to put into `Integral.kernel`.
 
     The reference generates a tabulate_tensor kernel per form at run time (runintgen / FFCx,
@@ -260,8 +269,31 @@ def register_integrand(name: str, source: str, rank: int = 2, facet: bool = Fals
 
     over (c0, lf0, c1, lf1) rows -- macro tensor [[00, 01], [10, 11]], both cells' coordinate_dofs, {lf0, lf1}
     (assemble_matrix_impl.h:528-542).  `variant=(tdim, dofs per cell[, bs])`: the variant the source is validated
-    against at registration (default (3, 4, 1))."""
+    against at registration (default (3, 4, 1)).
+
+    A bilinear integrand between two spaces (the off-diagonal blocks of `MixedSpace`, forms with a `trial_space`):
+    `variant=(tdim, nd0, bs0, nd1, bs1)`, or `variant=(tdim, nd0[, bs0])` with `trial=(nd1[, bs1])`
+    (cfx_integrand_register2).  Its tensor is [NDB0][NDB1] (cells) or [2 NDB0][2 NDB1] (interior facets), with
+    CFX_ND0 / CFX_BS0 / CFX_NDB0, CFX_ND1 / CFX_BS1 / CFX_NDB1 and cfx_tabulate0 / cfx_tabulate1 in scope."""
     kid = C.c_int()
+    two = trial is not None or (variant is not None and len(variant) == 5)
+    if two:
+        if rank != 2:
+            raise ValueError("register_integrand: an integrand between two spaces is bilinear")
+        if variant is None:
+            raise ValueError("register_integrand: `trial` goes with `variant=(tdim, nd0[, bs0])`")
+        if trial is not None:
+            if len(variant) > 3:
+                raise ValueError("register_integrand: give the trial space either in `variant` or in `trial`")
+            tdim, nd0, bs0 = (list(variant) + [1])[:3]
+            nd1, bs1 = (list(trial) + [1])[:2]
+        else:
+            tdim, nd0, bs0, nd1, bs1 = variant
+        _lib.check(_lib.load().cfx_integrand_register2(name.encode(), source.encode(), int(bool(facet)), int(tdim), int(nd0),
+                                                       int(bs0), int(nd1), int(bs1), C.byref(kid)))
+        _user_integrand_rank[kid.value] = 2
+        _user_integrand_two.add(kid.value)
+        return kid.value
     if variant is None and not facet:
         _lib.check(_lib.load().cfx_integrand_register(name.encode(), source.encode(), int(rank), C.byref(kid)))
     elif variant is None:
@@ -277,6 +309,12 @@ def register_integrand(name: str, source: str, rank: int = 2, facet: bool = Fals
 def compile_integrand(kernel_id: int, tdim: int, ndofs_cell: int, bs: int = 1) -> None:
     """Compile the (tdim, dofs per cell, block size) variant of a registered integrand now instead of at its first use."""
     _lib.check(_lib.load().cfx_integrand_compile_bs(int(kernel_id), int(tdim), int(ndofs_cell), int(bs)))
+
+
+def compile_integrand2(kernel_id: int, tdim: int, nd0: int, bs0: int, nd1: int, bs1: int) -> None:
+    """Compile the (tdim, test nd0 / bs0, trial nd1 / bs1) variant of a two-space integrand now instead of at its first
+    use (cfx_integrand_compile2)."""
+    _lib.check(_lib.load().cfx_integrand_compile2(int(kernel_id), int(tdim), int(nd0), int(bs0), int(nd1), int(bs1)))
 
 
 def form(integrals, V: FunctionSpace, rank: int | None = None, trial_space: FunctionSpace | None = None, dtype=None) -> CutForm:

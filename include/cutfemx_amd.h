@@ -520,6 +520,26 @@ int cfx_integrand_register_facet(const char* name, const char* source, int* kern
 int cfx_integrand_register_variant(const char* name, const char* source, int rank, int facet, int tdim, int ndofs_cell, int bs,
                                    int* kernel_id);
 int cfx_integrand_compile_bs(int kernel_id, int tdim, int ndofs_cell, int bs);
+/* Integrands of bilinear forms between two spaces (cfx_form_create2: test space nd0 dofs per cell, block size bs0;
+ * trial space nd1, bs1) -- the off-diagonal blocks of mixed systems.  The argument lists are those above; only the tensor
+ * shapes change.  Each variant is compiled with CFX_TDIM, CFX_ND0 CFX_BS0 CFX_NDB0 (test) and CFX_ND1 CFX_BS1 CFX_NDB1
+ * (trial) defined (CFX_ND / CFX_BS / CFX_NDB / cfx_tabulate are not: they name one space); cfx_tabulate0 / cfx_tabulate1
+ * give the basis of either space, cfx_tabulate_p1 / _p2, cfx_inverse_jacobian and cfx_cell_diameter stay in scope.
+ *   cell integrals (facet = 0): A is [NDB0][NDB1] row-major, entry (i, a; j, b) at (i * BS0 + a) * NDB1 + j * BS1 + b
+ *     (the layout cfx_tabulate_entity returns for cfx_form_create2 forms); standard cells and / or runtime rules, with
+ *     point_data;
+ *   interior facets (facet = 1): A is [2 NDB0][2 NDB1]: rows [cell 0, cell 1] test dofs, columns [cell 0, cell 1] trial
+ *     dofs; at most 24 macro dofs on each side.
+ * `w` is a scalar coefficient packed with the TEST space's dofmap.  A square form given a two-space id, or a two-space
+ * form given a square id, is CFX_ERR_INVALID_ARGUMENT.  The source is validated against the named variant.
+ *
+ * Registered interior-facet integrals (square or two-space) may also carry facet-hosted runtime rules (cfx_integral.rules
+ * from cfx_cut_create_facets with row_width 4): entity f >= the number of standard facets integrates over rule
+ * f - n_std, its points on the host facet's simplex pushed to physical space and pulled back to both cells, its weights
+ * as the rules store them -- rules of any length.  cfx_apply_lifting accepts every form with registered integrals. */
+int cfx_integrand_register2(const char* name, const char* source, int facet, int tdim, int nd0, int bs0, int nd1, int bs1,
+                            int* kernel_id);
+int cfx_integrand_compile2(int kernel_id, int tdim, int nd0, int bs0, int nd1, int bs1);
 
 /* ---- deactivation: cpp/cutfemx/fem/deactivate.h:387-418 ------------------- */
 /* active_domain(): the two indicators (active cells, active dofs) are the marks of the form's row plan; deactivation

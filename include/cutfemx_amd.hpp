@@ -502,6 +502,18 @@ inline int register_integrand(const std::string& name, const std::string& source
   return id;
 }
 
+/// A bilinear integrand between two spaces (cfx_integrand_register2): the tensor is [NDB0][NDB1] (cells) or
+/// [2 NDB0][2 NDB1] (interior facets, `facet` = true); (tdim, `test`, `trial`) = the variant the source is validated
+/// against.  The id goes into the Integral::kernel of forms made with two spaces.
+inline int register_integrand2(const std::string& name, const std::string& source, bool facet, int tdim,
+                               const FunctionSpace& test, const FunctionSpace& trial)
+{
+  int id = 0;
+  check(cfx_integrand_register2(name.c_str(), source.c_str(), facet ? 1 : 0, tdim, test.ndofs_cell, test.bs,
+                                trial.ndofs_cell, trial.bs, &id));
+  return id;
+}
+
 /// (Sync-free steps -- cfx_step_begin / cfx_step_end -- are not wrapped here: this facade returns host vectors sized by the
 /// counts of the moment, and inside a step those are capacities.  Callers that pass device handles on use the C ABI's
 /// step functions directly, as cutfemx_amd/step.py does.)
