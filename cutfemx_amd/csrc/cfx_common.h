@@ -685,6 +685,10 @@ struct VecBlocks
 };
 constexpr int kVbEntries = 2048;
 
+// Kuhn split of a hex into six tets: local vertex i of tet j is hex corner kKuhnTet[j][i], corner = bx + 2 by + 4 bz
+// (the table of cfx_mesh.hip's box generator; cfx_mesh_s::hex_groups)
+constexpr int kKuhnTet[6][4] = {{0, 1, 3, 7}, {0, 1, 5, 7}, {0, 2, 3, 7}, {0, 2, 6, 7}, {0, 4, 5, 7}, {0, 4, 6, 7}};
+
 } // namespace cfx
 
 struct cfx_mesh_s
@@ -706,6 +710,12 @@ struct cfx_mesh_s
   // generated box / slab mesh (cfx_mesh_create_box / _slab): box_n cubes per edge, Kuhn split, vertex id
   // ix + (n+1)(iy + (n+1) iz): the connectivity is a function of the cell id ("implicit-structured")
   int box_n = 0;
+  // Hex groups (tdim 3, decided when the mesh is created): cells 6h .. 6h+5 are the six Kuhn tets of hex h -- local
+  // vertex i of cell 6h+j is hex corner kKuhnTet[j][i] (corner 0 is local vertex 0 and corner 7 local vertex 3 of all
+  // six) -- and a vertex is corner k of at most one hex for every k.  hex_corners[v] bit k: v is corner k of some hex.
+  // A linear form then sums a hex's element vectors per corner in one lane (cfx_gather.hip, vec_source_groups_kernel).
+  bool hex_groups = false;
+  cfx::DevArray<uint8_t> hex_corners; // [nnodes]
   const cfx::DevArray<int32_t>& cell_neighbours();
   // Vertex summary of every block of kClassBlock consecutive cells (mesh-static, built on the first classification of a
   // level set that lives on the geometry dofmap): the distinct vertices of the block's cells as at most kClassRuns runs
@@ -888,6 +898,11 @@ struct cfx_row_plan
   cfx::Count vec_t2_total;
   int vec_fast = -1;
   uint8_t vec_mark = 0;
+  // ... or, for the series source term on a mesh of hex groups (cfx::source_groups_ok), one slot per hex corner: the
+  // value hex corner k adds to plain row r lives at k * vec_group_cap + vec_t2off[r] - 1, vec_t2off[r] - 1 = the
+  // position of r in plain_rows; the slots of a row are the bits of cfx_mesh_s::hex_corners
+  bool vec_groups = false;
+  int64_t vec_group_cap = 0;
   // linear forms by cell block (cfx::vec_block_plan, VecBlocks): the blocks that hold a cell with mark `vb_mark`, and
   // for every block the first of its partials in the step's compact partial array (-1: no such cell, no partials)
   cfx::DevArray<int32_t> vb_active; // blocks with an uncut entity
@@ -960,6 +975,7 @@ void plan_cut_cells(cfx_form_s* a);                                     // cfx_r
 const Stencil& space_stencil_tiles(cfx_space_s* V);                     // cfx_rowasm.hip
 bool space_dof_verts(cfx_space_s* V);                                   // cfx_rowasm.hip (cfx_space_s::dof_verts)
 bool plain_vec_offsets(cfx_form_s* L, uint8_t mark);                    // cfx_rowasm.hip
+bool source_groups_ok(cfx_form_s* L, uint8_t mark);                     // cfx_gather.hip
 const VecBlocks& space_vec_blocks(cfx_space_s* V);                      // cfx_rowasm.hip
 bool vec_block_plan(cfx_form_s* L, uint8_t mark, bool merged);          // cfx_rowasm.hip
 void build_pattern(cfx_form_s* a, cfx_pattern_s* P);                    // cfx_rowasm.hip

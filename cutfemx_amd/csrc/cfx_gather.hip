@@ -506,9 +506,12 @@ __device__ __forceinline__ void source_load_vertices(const VecArgs& A, SourceCel
   }
 }
 
+// x: the cell's vertices.  Sa / Ca: sincospi of vertex 0, when the caller has it already (the six tets of a hex share
+// vertex 0: vec_source_groups_kernel) -- the same values the series branch would compute
 template <int TDIM>
-__device__ __forceinline__ void source_vector(const SourceCell<TDIM>& c, int npts, const double* __restrict__ pts,
-                                              const double* __restrict__ wts, double fscale, double* be)
+__device__ __forceinline__ void source_vector(const double (&x)[TDIM + 1][TDIM], int npts, const double* __restrict__ pts,
+                                              const double* __restrict__ wts, double fscale, double* be,
+                                              const double* Sa = nullptr, const double* Ca = nullptr)
 {
   constexpr int ND = TDIM + 1;
   double ed[TDIM][TDIM]; // (x_{t+1} - x_0)_d
@@ -518,7 +521,7 @@ __device__ __forceinline__ void source_vector(const SourceCell<TDIM>& c, int npt
 #pragma unroll
     for (int d = 0; d < TDIM; ++d)
     {
-      ed[t][d] = c.x[t + 1][d] - c.x[0][d];
+      ed[t][d] = x[t + 1][d] - x[0][d];
       hmax = fmax(hmax, fabs(ed[t][d]));
     }
   double det;
@@ -538,7 +541,8 @@ __device__ __forceinline__ void source_vector(const SourceCell<TDIM>& c, int npt
 #pragma unroll
     for (int d = 0; d < TDIM; ++d)
     {
-      cfx_sincospi(c.x[0][d], S[d], C[d]);
+      if (Sa) { S[d] = Sa[d]; C[d] = Ca[d]; }
+      else cfx_sincospi(x[0][d], S[d], C[d]);
 #pragma unroll
       for (int t = 0; t < TDIM; ++t) ed[t][d] *= kPi;
     }
@@ -595,7 +599,7 @@ __device__ __forceinline__ void source_vector(const SourceCell<TDIM>& c, int npt
 #pragma unroll
       for (int d = 0; d < TDIM; ++d)
       {
-        double v = c.x[0][d];
+        double v = x[0][d];
 #pragma unroll
         for (int t = 0; t < TDIM; ++t) v = fma(X[t], ed[t][d], v);
         f *= cfx_sinpi(v);
@@ -613,7 +617,7 @@ __device__ __forceinline__ void source_compute(const VecArgs& A, const SourceCel
 {
   constexpr int ND = TDIM + 1;
   double be[ND];
-  source_vector<TDIM>(c, npts, pts, wts, fscale, be);
+  source_vector<TDIM>(c.x, npts, pts, wts, fscale, be);
   if (!valid) return;
   // entry i to the segment of row dof_i (store_std_vector, with the gathers already in registers)
   bool record = A.t2 == nullptr;
@@ -665,6 +669,100 @@ __global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_source_sin_p1_ke
     b = c;
     cell_c = cell_d;
   }
+}
+
+// The same source term by hex (cfx_row_plan::vec_groups, cfx_mesh_s::hex_groups): one lane per hex of the step's group
+// list (the position of the hex's first entity in the located list; its marked tets are that entity and the ones after
+// it with the same hex id).  The lane sums the tets' element vectors per hex corner in tet order and stores one value
+// per corner whose row is plain, in that corner's plane of the staging (8 coalesced stores per hex where the cell
+// kernel above made 24 scattered ones), with vertex 0's sincospi computed once for the six tets.  A tet with a corner
+// off the plain rows also writes the per-cell record (at its list position) that the other rows gather.
+// entity i of a located list starts a hex group
+struct GroupHead
+{
+  const int32_t* ent;
+  __device__ bool operator()(int64_t i) const { return i == 0 || ent[i - 1] / 6 != ent[i] / 6; }
+};
+
+struct GroupArgs
+{
+  const int32_t* first; // [ng] position of the hex's first entity in A.entities
+  DevN ng;
+  int64_t cap;          // corner plane stride of A.t2 (cfx_row_plan::vec_group_cap)
+};
+
+__global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_source_groups_kernel(VecArgs A, GroupArgs G)
+{
+  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g >= dev_n(G.ng)) return;
+  const int64_t n = dev_n(A.n), f = G.first[g];
+  int32_t ids[6];
+#pragma unroll
+  for (int m = 0; m < 6; ++m) ids[m] = A.entities[f + m < n ? f + m : n - 1];
+  const int32_t hex = ids[0] / 6;
+  unsigned mask = 0;
+#pragma unroll
+  for (int m = 0; m < 6; ++m)
+    if (f + m < n && ids[m] / 6 == hex) mask |= 1u << (ids[m] - 6 * hex);
+  // the eight corners from tets 0 {0,1,3,7}, 3 {0,2,6,7} and 4 {0,4,5,7}
+  const int4* conn4 = reinterpret_cast<const int4*>(A.conn) + 6 * (int64_t)hex;
+  const int4 r0 = conn4[0], r3 = conn4[3], r4 = conn4[4];
+  const int32_t cv[8] = {r0.x, r0.y, r3.y, r0.z, r4.y, r4.z, r3.z, r0.w};
+  // corners 0 and 7 (in every tet) stay in registers, a tet's middle corners are loaded as it comes.  The tet loop is
+  // not unrolled: the corner sums take a tet's values by selects (the unrolled loop spills at CFX_SOURCE_WAVES = 4)
+  double x0[3], x7[3];
+  load_vertex<3>(A.x, cv[0], x0);
+  load_vertex<3>(A.x, cv[7], x7);
+  // bit k: the row of corner k is plain (its slot is read again, from cache, when the sums are stored)
+  unsigned plain = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) plain |= A.t2off[cv[k]] != 0 ? 1u << k : 0u; // (stored + 1: 0 = the row is not plain)
+  int npts;
+  const double* wts;
+  const double* pts = ref_rule(3, A.qdegree, npts, wts);
+  const double fscale = A.params[1] * ((int)A.params[0] == CFX_F_POISSON_RHS ? 3.0 * kPi * kPi : 1.0);
+  double S[3], C[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) cfx_sincospi(x0[d], S[d], C[d]);
+  double acc[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) acc[k] = 0.0;
+  const int64_t stride = A.out_cells > 0 ? A.out_cells : A.n.cap;
+  // middle corners of tet j (kKuhnTet[j][1], kKuhnTet[j][2]): nibble j of these words
+  constexpr unsigned kMidA = 0x442211u, kMidB = 0x656353u;
+  int j = __builtin_ctz(mask);
+#pragma unroll 1
+  while (true)
+  {
+    const unsigned rest = mask & ~((2u << j) - 1u);
+    const int4 row = conn4[j];
+    double x[4][3];
+    load_vertex<3>(A.x, row.y, x[1]);
+    load_vertex<3>(A.x, row.z, x[2]);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { x[0][d] = x0[d]; x[3][d] = x7[d]; }
+    double be[4];
+    source_vector<3>(x, npts, pts, wts, fscale, be, S, C);
+    const int ka = (int)((kMidA >> (4 * j)) & 0xfu), kb = (int)((kMidB >> (4 * j)) & 0xfu);
+    acc[0] += be[0];
+    acc[7] += be[3];
+#pragma unroll
+    for (int k = 1; k < 7; ++k) acc[k] += k == ka ? be[1] : (k == kb ? be[2] : 0.0);
+    if ((plain & ((1u << ka) | (1u << kb) | 0x81u)) != ((1u << ka) | (1u << kb) | 0x81u))
+    {
+      const int64_t at = A.out_cells > 0 ? 6 * (int64_t)hex + j : f + __popc(mask & ((1u << j) - 1u));
+#pragma unroll
+      for (int i = 0; i < 4; ++i) A.out[(int64_t)i * stride + at] = be[i];
+    }
+    if (!rest) break;
+    j = __builtin_ctz(rest);
+  }
+  // (the corner ids again: the rows of tets 0, 3, 4 are in cache; holding them through the loop spills)
+  const int4 s0 = conn4[0], s3 = conn4[3], s4 = conn4[4];
+  const int32_t sv[8] = {s0.x, s0.y, s3.y, s0.z, s4.y, s4.z, s3.z, s0.w};
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (plain & (1u << k)) A.t2[(int64_t)k * G.cap + A.t2off[sv[k]] - 1] = acc[k];
 }
 
 // ---------------------------------------------------------------------------
@@ -913,7 +1011,7 @@ __global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_blocks_sin_p1_ke
     double be[ND];
 #pragma unroll
     for (int j = 0; j < ND; ++j) be[j] = 0.0;
-    if (__ballot(xa.on) != 0) source_vector<TDIM>(a, npts, pts, wts, fscale, be); // (a wavefront without a marked cell: the ends of a block)
+    if (__ballot(xa.on) != 0) source_vector<TDIM>(a.x, npts, pts, wts, fscale, be); // (a wavefront without a marked cell: the ends of a block)
     double* sv = s_val[buf];
     if ((int)threadIdx.x < xa.nb)
     {
@@ -3749,7 +3847,18 @@ void vec_tensors(cfx_form_s* L, const cfx_integral_dev& I, bool runtime, double*
   if (!runtime)
   {
     A.n = I.n_entities; A.entities = I.entities.p;
-    if (source_series_ok<DEG>(V, I))
+    cfx_row_plan& plan = row_plan(L);
+    if (TDIM == 3 && DEG == 1 && A.t2 && plan.vec_groups && source_series_ok<DEG>(V, I))
+    {
+      // by hex (the staging was laid out for it: cfx::plain_vec_offsets): the group list is the positions of the entities
+      // that start a hex, compacted from the list itself (ascending and without repeats: a located list)
+      DevArray<int32_t> first;
+      const Count ng = compact_count("source_groups", "vec.source_groups", A.n, GroupHead{A.entities}, first);
+      GroupArgs G{first.p, ng.devn(), plan.vec_group_cap};
+      if (ng.cap() > 0)
+        launch("vec_tensors_std", vec_source_groups_kernel, grid_for(ng.cap()), dim3(kBlock), 0, A, G);
+    }
+    else if (source_series_ok<DEG>(V, I))
     {
       if constexpr (DEG == 1)
       {
@@ -4452,6 +4561,28 @@ __global__ void __launch_bounds__(kWave) assemble_vec_plain_kernel(DevN n_plain_
   if (live && gl == 0 && o >= 0) b[r] += part;
 }
 
+// ... with hex groups (cfx_row_plan::vec_groups): plain row r = rows[i] adds its corner slots k * cap + i, k over the bits
+// of hex_corners[r] in ascending order (one lane per row; a lane's loads and its neighbours' are contiguous)
+__global__ void __launch_bounds__(kBlock) assemble_vec_plain_groups_kernel(DevN n_plain_d, const int32_t* __restrict__ rows,
+                                                                           const uint8_t* __restrict__ corners,
+                                                                           const int32_t* __restrict__ t2off,
+                                                                           const double* __restrict__ t2, int64_t cap,
+                                                                           double* __restrict__ b)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= dev_n(n_plain_d) || i >= cap) return;
+  const int64_t r = rows[i];
+  if (t2off[r] == 0) return; // (a plain row whose cells do not all carry the mark: the per-cell records)
+  const unsigned m = corners[r];
+  double v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = (m >> k) & 1u ? t2[k * cap + i] : 0.0;
+  double sum = v[0];
+#pragma unroll
+  for (int k = 1; k < 8; ++k) sum += v[k];
+  b[r] += sum;
+}
+
 // Which way the uncut cells and rules of a linear form reach the rows.  The series source term on a P1 space keeps the
 // row-ordered staging when the plan offers it (512^3: 2.65 + 0.73 ms against 2.8 + 0.55 ms by cell block, and the
 // rule items by row 0.6 ms against 0.85 ms by block); every other form goes by cell block, uncut entities and rule
@@ -4503,7 +4634,7 @@ void run_vector(cfx_form_s* L, double* b)
     if (!st.vec_blocks && count == 1 && L->V->bs == 1 && plan.usable && !(ro && ro[0] == '0') && !has_user
         && plain_vec_offsets(L, (uint8_t)(1u << slot)))
     {
-      st.t2.alloc(plan.vec_t2_total.cap());
+      st.t2.alloc(plan.vec_groups ? 8 * plan.vec_group_cap : plan.vec_t2_total.cap());
       st.vec_t2 = st.t2.p;
     }
   }
@@ -4535,9 +4666,13 @@ void run_vector(cfx_form_s* L, double* b)
   if (st.vec_t2)
   {
     constexpr int G = CFX_VEC_PLAIN_G;
-    launch("assemble_vec_plain", assemble_vec_plain_kernel<G>,
-           dim3((unsigned)((plan.n_plain_rows.cap() + (kWave / G) - 1) / (kWave / G))), dim3(kWave), 0, plan.n_plain_rows,
-           plan.plain_rows.p, A.d2c_off, plan.vec_t2off.p, st.vec_t2, b);
+    if (plan.vec_groups)
+      launch("assemble_vec_plain", assemble_vec_plain_groups_kernel, grid_for(plan.n_plain_rows.cap()), dim3(kBlock), 0,
+             plan.n_plain_rows, plan.plain_rows.p, L->V->mesh->hex_corners.p, plan.vec_t2off.p, st.vec_t2, plan.vec_group_cap, b);
+    else
+      launch("assemble_vec_plain", assemble_vec_plain_kernel<G>,
+             dim3((unsigned)((plan.n_plain_rows.cap() + (kWave / G) - 1) / (kWave / G))), dim3(kWave), 0, plan.n_plain_rows,
+             plan.plain_rows.p, A.d2c_off, plan.vec_t2off.p, st.vec_t2, b);
     // everything else gathers the per-cell records: the rows next to the interface ...
     A.n_active = plan.n_special_rows; A.active_rows = plan.special_rows.p;
     if (plan.n_vec_odd_rows.cap() > 0)
@@ -4561,6 +4696,25 @@ void run_vector(cfx_form_s* L, double* b)
 
 namespace cfx
 {
+
+// the series source term of the uncut entities of cell integral slot `mark` on a P1 space over a mesh of hex groups,
+// its entity list a located list as handed out: the staging by hex corner (cfx_row_plan::vec_groups).
+// CFX_SOURCE_GROUPS=0: never (the per-cell kernel and segments)
+bool source_groups_ok(cfx_form_s* L, uint8_t mark)
+{
+  const char* e = getenv("CFX_SOURCE_GROUPS");
+  if (e && e[0] == '0') return false;
+  cfx_space_s* V = L->V;
+  if (!V->mesh->hex_groups || V->mesh->tdim != 3 || V->degree != 1 || V->bs != 1 || mark == 0 || (mark & 0x0Fu) != mark)
+    return false;
+  cfx_row_plan& plan = row_plan(L);
+  const int slot = __builtin_ctz(mark);
+  if ((mark & (mark - 1)) != 0 || slot >= plan.n_cell_slots) return false;
+  const cfx_integral_dev& I = L->integrals[plan.cell_slot_integral[slot]];
+  if (user_integrand_known(I.kernel) || !source_series_ok<1>(V, I) || I.n_entities.cap() == 0) return false;
+  const ListProvenance* pv = provenance_lookup(I.entities.p);
+  return pv && pv->n == I.n_entities.key() && pv->cut->gen == pv->gen && pv->cut->mesh == V->mesh;
+}
 
 // ---------------------------------------------------------------------------
 // Rectangular blocks (test space != trial space, cfx_form_create2) by row gather: the work units of the entity-parallel

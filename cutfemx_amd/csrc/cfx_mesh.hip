@@ -64,6 +64,89 @@ __global__ void box_cells_kernel(int tdim, int n, int64_t ncells, int32_t* __res
   *reinterpret_cast<int4*>(conn + c * 4) = make_int4(v[0], v[1], v[2], v[3]);
 }
 
+// cfx_mesh_s::hex_groups of a generated box / slab mesh (n x n x nz hexes, vertex ix + (n+1)(iy + (n+1) iz)): vertex
+// (ix, iy, iz) is corner (bx, by, bz) of hex (ix - bx, iy - by, iz - bz) when that hex exists
+__global__ void box_hex_corners_kernel(int n, int nz, int64_t nnodes, uint8_t* __restrict__ corners)
+{
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= nnodes) return;
+  const int64_t n1 = n + 1;
+  const int64_t ix = v % n1, iy = (v / n1) % n1, iz = v / (n1 * n1);
+  unsigned m = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+  {
+    const int64_t hx = ix - (k & 1), hy = iy - ((k >> 1) & 1), hz = iz - ((k >> 2) & 1);
+    if (hx >= 0 && hx < n && hy >= 0 && hy < n && hz >= 0 && hz < nz) m |= 1u << k;
+  }
+  corners[v] = (uint8_t)m;
+}
+
+// ... of any other mesh: the corners of hex h read from its six cells, which must follow the Kuhn pattern (every corner
+// one vertex, eight distinct vertices); bit k of corner32[v] is set by the hex whose corner k is v -- a second such
+// hex, or a cell off the pattern, sets *bad
+__global__ void hex_corners_check_kernel(const int32_t* __restrict__ conn, int64_t nhex, unsigned* __restrict__ corner32,
+                                         int* __restrict__ bad)
+{
+  const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= nhex) return;
+  int32_t cv[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) cv[k] = -1;
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j)
+  {
+    const int4 r = *reinterpret_cast<const int4*>(conn + (6 * h + j) * 4);
+    const int32_t v[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+    {
+      const int k = kKuhnTet[j][i];
+      if (v[i] < 0) ok = false;
+      else if (cv[k] < 0) cv[k] = v[i];
+      else if (cv[k] != v[i]) ok = false;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 8; ++a)
+#pragma unroll
+    for (int b = a + 1; b < 8; ++b) ok = ok && cv[a] != cv[b];
+  if (!ok) { *bad = 1; return; }
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (atomicOr(corner32 + cv[k], 1u << k) & (1u << k)) *bad = 1;
+}
+
+__global__ void pack_corners_kernel(int64_t nnodes, const unsigned* __restrict__ corner32, uint8_t* __restrict__ corners)
+{
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < nnodes) corners[v] = (uint8_t)corner32[v];
+}
+
+void hex_groups_box(cfx_mesh_s& m, int n, int nz)
+{
+  m.hex_corners.alloc(m.nnodes);
+  launch("hex_groups", box_hex_corners_kernel, grid_for(m.nnodes), dim3(kBlock), 0, n, nz, m.nnodes, m.hex_corners.p);
+  m.hex_groups = true;
+}
+
+// (at creation: the one read-back can never fall inside a step)
+void hex_groups_check(cfx_mesh_s& m)
+{
+  if (m.tdim != 3 || m.ncells == 0 || m.ncells % 6 != 0) return;
+  const int64_t nhex = m.ncells / 6;
+  DevArray<unsigned> c32(m.nnodes);
+  dev_fill(c32.p, 0, sizeof(unsigned) * (size_t)m.nnodes);
+  DevArray<int> bad(1);
+  dev_fill(bad.p, 0, sizeof(int));
+  launch("hex_groups", hex_corners_check_kernel, grid_for(nhex), dim3(kBlock), 0, m.conn.p, nhex, c32.p, bad.p);
+  if (read_scalar(bad.p) != 0) return;
+  m.hex_corners.alloc(m.nnodes);
+  launch("hex_groups", pack_corners_kernel, grid_for(m.nnodes), dim3(kBlock), 0, m.nnodes, c32.p, m.hex_corners.p);
+  m.hex_groups = true;
+}
+
 } // namespace
 
 extern "C" {
@@ -95,6 +178,7 @@ int cfx_mesh_create(int tdim, int gdim, int64_t nnodes, const double* x, int64_t
            cell_stride, m->conn.p);
     CFX_HIP(hipStreamSynchronize(ctx().stream));
   }
+  hex_groups_check(*m);
   *out = m.release();
   CFX_API_END
 }
@@ -117,6 +201,7 @@ int cfx_mesh_create_box(int tdim, int n, cfx_mesh_t* out)
   m->box_n = n;
   launch("box_nodes", box_nodes_kernel, grid_for(nnodes), dim3(kBlock), 0, tdim, n, 0, nnodes, m->x.p);
   launch("box_cells", box_cells_kernel, grid_for(ncells), dim3(kBlock), 0, tdim, n, ncells, m->conn.p);
+  if (tdim == 3) hex_groups_box(*m, n, n);
   *out = m.release();
   CFX_API_END
 }
@@ -139,6 +224,7 @@ int cfx_mesh_create_slab(int n, int z0, int nz, cfx_mesh_t* out)
   m->box_n = n;
   launch("box_nodes", box_nodes_kernel, grid_for(nnodes), dim3(kBlock), 0, 3, n, z0, nnodes, m->x.p);
   launch("box_cells", box_cells_kernel, grid_for(ncells), dim3(kBlock), 0, 3, n, ncells, m->conn.p);
+  hex_groups_box(*m, n, nz);
   *out = m.release();
   CFX_API_END
 }

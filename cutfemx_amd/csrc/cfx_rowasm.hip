@@ -2958,13 +2958,15 @@ __global__ void vec_plain_len_kernel(DevN n_plain_d, const int32_t* __restrict__
   len[i] = l > 0 ? l : (1ll << 32);
 }
 
+// by_row (hex groups, cfx_row_plan::vec_groups): the row's position in the plain-row list instead of its segment offset
 __global__ void vec_plain_scatter_kernel(DevN n_plain_d, const int32_t* __restrict__ rows, const int64_t* __restrict__ off,
-                                         int32_t* __restrict__ t2off)
+                                         int32_t* __restrict__ t2off, bool by_row)
 {
   const int64_t n_plain = dev_n(n_plain_d);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   // (entries in the low 32 bits of the packed prefix)
-  if (i < n_plain && (off[i + 1] & 0xffffffffll) > (off[i] & 0xffffffffll)) t2off[rows[i]] = (int32_t)(off[i] & 0xffffffffll) + 1;
+  if (i < n_plain && (off[i + 1] & 0xffffffffll) > (off[i] & 0xffffffffll))
+    t2off[rows[i]] = (by_row ? (int32_t)i : (int32_t)(off[i] & 0xffffffffll)) + 1;
 }
 
 
@@ -2973,8 +2975,9 @@ __global__ void vec_plain_scatter_kernel(DevN n_plain_d, const int32_t* __restri
 __global__ void __launch_bounds__(kBlock) vec_plain_offsets_chained_kernel(DevN n_plain_d, const int32_t* __restrict__ rows,
                                                                            const int64_t* __restrict__ d2c_off,
                                                                            const uint8_t* __restrict__ uniform, uint8_t mark,
-                                                                           int32_t* __restrict__ t2off, ChainState chain,
-                                                                           int64_t* __restrict__ total_out, CountJobs after)
+                                                                           int32_t* __restrict__ t2off, bool by_row,
+                                                                           ChainState chain, int64_t* __restrict__ total_out,
+                                                                           CountJobs after)
 {
   const int64_t n_plain = dev_n(n_plain_d);
   const unsigned int tile = chain_take_tile(chain.ticket);
@@ -3002,7 +3005,7 @@ __global__ void __launch_bounds__(kBlock) vec_plain_offsets_chained_kernel(DevN 
   for (int k = 0; k < kScanItems; ++k)
   {
     // (entries in the low 32 bits of the packed prefix)
-    if ((l[k] & 0xffffffffll) > 0) t2off[r[k]] = (int32_t)(off & 0xffffffffll) + 1;
+    if ((l[k] & 0xffffffffll) > 0) t2off[r[k]] = (by_row ? (int32_t)(base + k) : (int32_t)(off & 0xffffffffll)) + 1;
     off += l[k];
   }
   if (tile == gridDim.x - 1 && threadIdx.x == kBlock - 1)
@@ -3028,12 +3031,16 @@ __global__ void gather_i32_kernel(DevN n_d, const int32_t* __restrict__ idx, con
 bool plain_vec_offsets(cfx_form_s* L, uint8_t mark)
 {
   cfx_row_plan& plan = row_plan(L);
-  if (plan.vec_fast >= 0 && plan.vec_mark == mark) return plan.vec_fast == 1;
+  // hex groups: the staging holds 8 corner planes of the plain rows (vec_source_groups_kernel) instead of segments
+  const bool groups = source_groups_ok(L, mark);
+  if (plan.vec_fast >= 0 && plan.vec_mark == mark && plan.vec_groups == groups) return plan.vec_fast == 1;
   plan.vec_mark = mark;
+  plan.vec_groups = groups;
   plan.vec_fast = 0;
   cfx_space_s* V = L->V;
   const Stencil& st = space_stencil(V);
   const int64_t n = plan.n_plain_rows.cap(); // (capacity while the length is in HBM)
+  plan.vec_group_cap = n;
   if (!st.usable || n == 0 || !plan.any_cells) return false;
   plain_row_masks(L);
   if (plan.plain_uniform.n != n) return false;
@@ -3073,10 +3080,10 @@ bool plain_vec_offsets(cfx_form_s* L, uint8_t mark)
   plan.vec_t2off_used = true;
   if (chain.state)
     launch("vec_plain_offsets", vec_plain_offsets_chained_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, plan.n_plain_rows,
-           plan.plain_rows.p, adj.offsets.p, plan.plain_uniform.p, mark, plan.vec_t2off.p, chain, off.p + n, after);
+           plan.plain_rows.p, adj.offsets.p, plan.plain_uniform.p, mark, plan.vec_t2off.p, groups, chain, off.p + n, after);
   else
     launch("vec_plain_offsets", vec_plain_scatter_kernel, grid_for(n), dim3(kBlock), 0, plan.n_plain_rows, plan.plain_rows.p,
-           off.p, plan.vec_t2off.p);
+           off.p, plan.vec_t2off.p, groups);
   // everything else reads the per-cell records: the special rows, and (a second pass that skips the rows with a
   // segment) the few plain rows whose cells do not all carry the mark
   plan.n_vec_odd_rows = tot[1];
