@@ -2862,7 +2862,9 @@ bool plain_row_masks(cfx_form_s* a, int32_t* counts, int* maxlen)
   plan.plain_masks_built = true;
   cfx_space_s* V = a->V;
   const Stencil& st = space_stencil(V);
-  const int64_t np = plan.n_plain_rows.cap(); // (capacity of the list while its length is in HBM)
+  // (capacity of the list while its length is in HBM; Count::key(): the same length after a read-back in mid-step, so
+  // that plain_vec_offsets, which may run after one, finds the masks it lays its staging out on)
+  const int64_t np = plan.n_plain_rows.key();
   if (!st.usable || np == 0 || !plan.any_cells) return false;
   const Adjacency& adj = V->dof_cells();
   plan.plain_masks.alloc(np);
@@ -2943,14 +2945,15 @@ void plan_cut_cells(cfx_form_s* a)
 // lengths of the dof->cells lists of the plain rows whose incident cells all carry `mark` (0 for the others:
 // rows at the edge of a restricted entity list, e.g. a rank's owned cells, keep the per-cell records)
 // (packed for one scan: segment entries in the low 32 bits, "this row has no segment" in the high ones)
-__global__ void vec_plain_len_kernel(DevN n_plain_d, const int32_t* __restrict__ rows, const int64_t* __restrict__ d2c_off,
-                                     const uint8_t* __restrict__ uniform, uint8_t mark, int64_t* __restrict__ len)
+__global__ void vec_plain_len_kernel(DevN n_plain_d, int64_t n_scan, const int32_t* __restrict__ rows,
+                                     const int64_t* __restrict__ d2c_off, const uint8_t* __restrict__ uniform, uint8_t mark,
+                                     int64_t* __restrict__ len)
 {
   const int64_t n_plain = dev_n(n_plain_d);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_plain)
   {
-    if (i < n_plain_d.cap) len[i] = 0; // (the scan runs over the capacity of the list)
+    if (i < n_scan) len[i] = 0; // (the scan runs over n_scan: the list's Count::key() length)
     return;
   }
   const int64_t r = rows[i];
@@ -3039,7 +3042,10 @@ bool plain_vec_offsets(cfx_form_s* L, uint8_t mark)
   plan.vec_fast = 0;
   cfx_space_s* V = L->V;
   const Stencil& st = space_stencil(V);
-  const int64_t n = plan.n_plain_rows.cap(); // (capacity while the length is in HBM)
+  // (capacity while the length is in HBM; Count::key(): a read-back in mid-step, between the matrix that built the
+  // plain-row masks and this linear form, must not change the length of the layout -- the staging fell back to the
+  // per-cell records then)
+  const int64_t n = plan.n_plain_rows.key();
   plan.vec_group_cap = n;
   if (!st.usable || n == 0 || !plan.any_cells) return false;
   plain_row_masks(L);
@@ -3064,7 +3070,7 @@ bool plain_vec_offsets(cfx_form_s* L, uint8_t mark)
   else
   {
     len.alloc(n);
-    launch("vec_plain_offsets", vec_plain_len_kernel, grid_for(n), dim3(kBlock), 0, plan.n_plain_rows, plan.plain_rows.p,
+    launch("vec_plain_offsets", vec_plain_len_kernel, grid_for(n), dim3(kBlock), 0, plan.n_plain_rows, n, plan.plain_rows.p,
            adj.offsets.p, plan.plain_uniform.p, mark, len.p);
     exclusive_scan(len.p, off.p, n, &cp);
   }

@@ -106,6 +106,17 @@ def oracle_dg_poisson(O, mesh, phi, degree=1, order=4, sigma=10.0, sigma_gamma=2
                 facet_rules=facet_rules, ghost=ghost, a=a, L=L)
 
 
+def groups_expected() -> bool:
+    """Whether the P1 series source term of a located list on a mesh of Kuhn hexes takes the hex-grouped kernel
+    (`source_groups`).  The diagnostic modes that switch it, the row stencil, the row-ordered staging or the series
+    kernel off, or send linear forms by cell block or through the entity-parallel atomics, take the per-cell path
+    with the same results."""
+    import os
+    env = os.environ.get
+    return not (env("CFX_SOURCE_GROUPS") == "0" or env("CFX_STENCIL") == "0" or env("CFX_VEC_BLOCKS") == "2"
+                or env("CFX_VEC_ROWORDER") == "0" or env("CFX_SOURCE_SERIES") == "0" or env("CFX_ASSEMBLY") == "atomic")
+
+
 def profiled(fn):
     """fn() with the engine's per-kernel profile on: (result, {kernel name: launches})."""
     import ctypes as C

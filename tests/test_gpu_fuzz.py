@@ -4,7 +4,7 @@ measure must give zero weights, never NaN), on unstructured meshes.  Integers bi
 import numpy as np
 import pytest
 
-from helpers import oracle_poisson, rel_err, scrambled_mesh
+from helpers import groups_expected, oracle_poisson, profiled, rel_err, scrambled_mesh
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-12
@@ -67,10 +67,15 @@ def test_degenerate_level_sets_match_oracle(oracle, tdim, n, seed):
         assert np.max(np.abs(R.points - want.points), initial=0.0) < 1e-13
 
 
-@pytest.mark.parametrize("tdim,n,degree,bs,margin", [(3, 8, 1, 1, None), (2, 16, 1, 1, None), (3, 5, 2, 1, None), (3, 6, 1, 3, None),
-                                                     (3, 40, 1, 1, None), (3, 20, 2, 1, None),
-                                                     (3, 8, 1, 1, 0.98), (3, 24, 1, 1, 0.97), (3, 6, 2, 1, 0.98)])
-def test_wandering_level_set_in_steps_equals_the_plain_sequence(tdim, n, degree, bs, margin):
+@pytest.mark.parametrize("tdim,n,degree,bs,margin,mesh_kind", [
+    pytest.param(*c, "scrambled" if c[4] is not None else "arrays", id="-".join(map(str, c)))
+    for c in [(3, 8, 1, 1, None), (2, 16, 1, 1, None), (3, 5, 2, 1, None), (3, 6, 1, 3, None),
+              (3, 40, 1, 1, None), (3, 20, 2, 1, None),
+              (3, 8, 1, 1, 0.98), (3, 24, 1, 1, 0.97), (3, 6, 2, 1, 0.98)]] + [
+    # forced margins on Kuhn-ordered meshes (from_arrays, generated box, generated slab): void steps on the hex-grouped
+    # source term; and a moving sphere at h = 1/128, in the band of its u^7 series
+    (3, 12, 1, 1, 0.97, "arrays"), (3, 12, 1, 1, 0.97, "box"), (3, 12, 1, 1, 0.97, "slab"), (3, 128, 1, 1, 0.97, "slab")])
+def test_wandering_level_set_in_steps_equals_the_plain_sequence(oracle, tdim, n, degree, bs, margin, mesh_kind):
     """Differential run (tools/soak_fuzz.py is the long form): a level set that wanders, breathes, leaves the mesh and
     swallows it; every step is run as a sync-free step (sizes from the previous step, voided and repeated when they do
     not fit, python/demo/demo_moving_poisson.py:53-90) and as the plain sequence -- the CSR pattern must agree bit for
@@ -82,16 +87,22 @@ def test_wandering_level_set_in_steps_equals_the_plain_sequence(tdim, n, degree,
     from cutfemx_amd import poisson
     fem = cfx.fem
     rng = np.random.default_rng(17 * tdim + n)
-    x, conn = cfx.box_mesh_arrays(tdim, n)
-    if margin is not None:
-        # capacities BELOW the previous counts (nearly every speculative pass is void) on a mesh without locality: vertices
-        # and cells renumbered at random (tools/soak_fuzz.py seed 31 faulted here: a row-pointer pass over garbage lengths)
-        pv = rng.permutation(x.shape[0])
-        inv = np.empty_like(pv)
-        inv[pv] = np.arange(pv.size)
-        x = x[pv]
-        conn = np.ascontiguousarray(inv[conn][rng.permutation(conn.shape[0])]).astype(np.int32)
-    mesh = cfx.Mesh.from_arrays(tdim, x, conn)
+    if mesh_kind in ("box", "slab"):
+        # generated in HBM (the box table of cfx_mesh_s::hex_corners); the slab: middle layers of the n^3 box
+        nz = 4 if n < 64 else 2
+        mesh = cfx.Mesh.create_box(tdim, n) if mesh_kind == "box" else cfx.Mesh.create_slab(n, n // 2 - nz // 2, nz)
+        x, conn = mesh.x, mesh.conn
+    else:
+        x, conn = cfx.box_mesh_arrays(tdim, n)
+        if mesh_kind == "scrambled":
+            # capacities BELOW the previous counts (nearly every speculative pass is void) on a mesh without locality: vertices
+            # and cells renumbered at random (tools/soak_fuzz.py seed 31 faulted here: a row-pointer pass over garbage lengths)
+            pv = rng.permutation(x.shape[0])
+            inv = np.empty_like(pv)
+            inv[pv] = np.arange(pv.size)
+            x = x[pv]
+            conn = np.ascontiguousarray(inv[conn][rng.permutation(conn.shape[0])]).astype(np.int32)
+        mesh = cfx.Mesh.from_arrays(tdim, x, conn)
     Vphi = cfx.FunctionSpace(mesh, 1)
     V = Vphi if (degree == 1 and bs == 1) else cfx.FunctionSpace(mesh, degree, bs=bs)
     xt = torch.tensor(x[:, :tdim].copy(), device="cuda")
@@ -126,13 +137,40 @@ def test_wandering_level_set_in_steps_equals_the_plain_sequence(tdim, n, degree,
         cfx.set_step_margin(margin, 0)
     sa, sb = {"cd": None}, {"cd": None}
     c, R, compared, refused = np.full(tdim, 0.5), 0.3, 0, 0
+    # Kuhn-ordered meshes with forced margins: the group path must run in void and repeated steps, and every 8th accepted
+    # step is checked against the oracle as well (an error of a path that both sides take escapes the differential)
+    watch = None
+    if margin is not None and mesh_kind != "scrambled":
+        om = oracle.Mesh(tdim, x, conn)
+        watch = {"passes": 0, "groups": 0, "groups_repeated": 0, "oracle": 0}
+
+        def check(i, A1, b1, d1, info, names):
+            # (names: the launches of the accepted pass)
+            watch["passes"] = max(watch["passes"], info["passes"])
+            watch["groups"] += "source_groups" in names
+            watch["groups_repeated"] += "source_groups" in names and info["passes"] > 1
+            if i % 8 == 0:
+                ref = oracle_poisson(oracle, om, phi.cpu().numpy(), order=3)
+                vals, bb = ref["values"].copy(), ref["b"].copy()
+                oracle.deactivate(ref["inactive"], ref["indptr"], ref["indices"], vals, bb)
+                assert np.array_equal(A1.indptr, ref["indptr"]) and np.array_equal(A1.indices, ref["indices"]), i
+                assert rel_err(A1.data, vals) < RTOL and rel_err(np.asarray(b1), bb) < RTOL, i
+                assert np.array_equal(d1.inactive_dofs, ref["inactive"]), i
+                watch["oracle"] += 1
     try:
-        _wander(cfx, rng, tdim, xt, phi, one, sa, sb, key, c, R)
+        _wander(cfx, rng, tdim, xt, phi, one, sa, sb, key, c, R, None if watch is None else check)
     finally:
         cfx.set_step_margin()
+    if watch is not None:
+        import os
+        assert watch["oracle"] >= 3, watch
+        speculate = os.environ.get("CFX_STEP_SPECULATE") != "0"
+        assert watch["passes"] > 1 or not speculate, watch
+        assert (watch["groups"] > 0) == groups_expected(), watch
+        assert (watch["groups_repeated"] > 0) == (groups_expected() and speculate), watch   # (after a void pass)
 
 
-def _wander(cfx, rng, tdim, xt, phi, one, sa, sb, key, c, R):
+def _wander(cfx, rng, tdim, xt, phi, one, sa, sb, key, c, R, check=None):
     import torch
     compared = refused = 0
     for k in range(48):
@@ -144,7 +182,17 @@ def _wander(cfx, rng, tdim, xt, phi, one, sa, sb, key, c, R):
             R = 2.0            # the whole mesh inside: no cut cell
         phi.copy_(torch.linalg.norm(xt - torch.tensor(c, device="cuda"), dim=1) - R)
         try:
-            A1, b1, d1 = cfx.run_step(lambda: one(sa), key=key)
+            if check is None:
+                A1, b1, d1 = cfx.run_step(lambda: one(sa), key=key)
+            else:
+                from cutfemx_amd import _lib
+                info = {}
+
+                def body():
+                    # the profile of the last pass only, the accepted one (a void pass launches the group list too)
+                    _lib.check(_lib.lib().cfx_profile_reset())
+                    return one(sa)
+                (A1, b1, d1), names = profiled(lambda: cfx.run_step(body, key=key, info=info))
         except ValueError as e:
             assert "no active background cells" in str(e) and float(phi.min()) > 0.0, (k, R, str(e))
             with pytest.raises(ValueError, match="no active background cells"):
@@ -159,6 +207,8 @@ def _wander(cfx, rng, tdim, xt, phi, one, sa, sb, key, c, R):
         if b1 is not None:
             assert rel_err(np.asarray(b1), np.asarray(b2)) < RTOL, (k, R)
         assert np.array_equal(d1.inactive_dofs, d2.inactive_dofs), (k, R)
+        if check is not None:
+            check(compared, A1, b1, d1, info, names)
         compared += 1
         del A1, b1, d1, A2, b2, d2
     assert compared >= 24 and refused >= 2, (compared, refused)

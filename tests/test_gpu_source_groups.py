@@ -1,10 +1,12 @@
 """The P1 series source term by hex (cfx_mesh_s::hex_groups, vec_source_groups_kernel): b against the oracle on the
 meshes where the group path is taken, against the per-cell path (CFX_SOURCE_GROUPS=0), bit for bit between two runs,
 and the per-cell path on a mesh that is not made of Kuhn hexes in order."""
+import os
+
 import numpy as np
 import pytest
 
-from helpers import level_set_values, oracle_poisson, profiled, rel_err, scrambled_mesh
+from helpers import groups_expected, level_set_values, oracle_poisson, profiled, rel_err, scrambled_mesh
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-12
@@ -28,6 +30,7 @@ def _check(O, om, mesh, phi, grouped):
     sysm = _system(mesh, phi)
     b, names = _b(sysm)
     assert rel_err(b, ref["b"]) < RTOL
+    grouped = grouped and groups_expected()          # (the diagnostic modes take the cell path: same values)
     assert ("source_groups" in names) == grouped, " ".join(sorted(names))
     if grouped:
         assert "vec_tensors_std" in names and "assemble_vec_plain" in names, " ".join(sorted(names))
@@ -68,9 +71,13 @@ def test_groups_match_cell_path_and_repeat(oracle, monkeypatch):
     sysm = _system(cfx.Mesh.create_box(3, 20), phi)
     b1, n1 = _b(sysm)
     b2, _ = _b(sysm)
-    assert "source_groups" in n1
-    assert np.array_equal(b1, b2)                      # fixed summation order: bit for bit
+    want = groups_expected()                           # (the mode of the run, before the switch below)
+    assert ("source_groups" in n1) == want
+    if os.environ.get("CFX_ASSEMBLY") == "atomic":      # (FP64 atomics: the order of the sums is the schedule's)
+        assert rel_err(b1, b2) < 1e-13
+    else:
+        assert np.array_equal(b1, b2)                  # fixed summation order: bit for bit
     monkeypatch.setenv("CFX_SOURCE_GROUPS", "0")
     b0, n0 = _b(sysm)
-    assert "source_groups" not in n0 and "vec_tensors_std" in n0
+    assert "source_groups" not in n0 and ("vec_tensors_std" in n0 or not want)
     assert rel_err(b1, b0) < 1e-13
