@@ -148,6 +148,11 @@ cfx_form_s* sub_form(cfx_form_s* a, const std::vector<int>& which)
     J.entities = alias(I.entities); J.n_entities = I.n_entities; J.rules = I.rules;
     J.entities_serial = I.entities_serial; J.rules_serial = I.rules_serial; J.n_std = I.n_std;
     J.point_data = alias(I.point_data); J.coefficient = alias(I.coefficient);
+    for (const cfx_coefficient_dev& c : I.coefficients) // (cfx_form_set_coefficients refreshes these aliases)
+    {
+      J.coefficients.emplace_back();
+      J.coefficients.back().space = c.space; J.coefficients.back().values = alias(c.values);
+    }
     for (int k = 0; k < 8; ++k) J.params[k] = I.params[k];
     f->integrals.push_back(std::move(J));
   }

@@ -838,6 +838,13 @@ struct cfx_space_s
   }
 };
 
+// one Function of an integral's coefficient list (cfx_form_set_coefficients): its space and its dof values
+struct cfx_coefficient_dev
+{
+  cfx_space_t space = nullptr;
+  cfx::DevArray<double> values; // [space ndofs * bs]: a copy of host values, an alias of device ones
+};
+
 struct cfx_integral_dev
 {
   int type = 0, kernel = 0, qdegree = 0, point_stride = 0;
@@ -848,6 +855,9 @@ struct cfx_integral_dev
   int64_t n_std = -1; // interior-facet integrals with facet-hosted rules: entities [n_std, n_entities) are the rules' rows (-1: none)
   cfx::DevArray<double> point_data;
   cfx::DevArray<double> coefficient; // dof values of a CFX_F_COEFFICIENT field
+  // registered integrands: the ordered list of Functions packed into `w`, each through its own space's dofmap; while it
+  // is not empty it replaces `coefficient` (stage 1 of cfx_rtc.hip is its only reader)
+  std::vector<cfx_coefficient_dev> coefficients;
   double params[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -992,6 +1002,7 @@ bool user_integrand_known(int kernel);
 int user_integrand_rank(int kernel);
 int user_integrand_kind(int kernel); // 0: cell integrand, 1: interior-facet integrand
 bool user_integrand_two(int kernel);  // registered with cfx_integrand_register2: serves forms between two spaces
+void user_coefficients_check(const cfx_form_s* a, const cfx_integral_dev& I); // the list of I: limits of `w`, compiled shapes
 void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* out, int64_t only_index = -1);
 void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, double* out, int out_mode, int64_t out_stride,
                  int64_t only_index = -1);

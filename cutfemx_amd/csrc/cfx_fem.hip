@@ -2097,6 +2097,61 @@ int cfx_form_prepare(cfx_form_t a)
   CFX_API_END
 }
 
+// Form::coefficients() of one integral: an ordered list of Functions, each on its own space (pack_form.h:69-158).  The
+// list lives with the integral; stage 1 of the registered integrands (cfx_rtc.hip) gathers it in-thread, so every
+// consumer of stage 1 -- row gather, scatter, tabulate, vectors, lifting -- sees it.  No read-back, no new row plan.
+int cfx_form_set_coefficients(cfx_form_t a, int integral, int n, const cfx_coefficient* coeffs)
+{
+  CFX_API_BEGIN
+  ctx().ensure();
+  require(a != nullptr, CFX_ERR_INVALID_ARGUMENT, "cfx_form_set_coefficients: null form");
+  require(integral >= 0 && integral < (int)a->integrals.size(), CFX_ERR_INVALID_ARGUMENT,
+          "cfx_form_set_coefficients: integral index out of range");
+  require(n >= 0 && n <= 8, CFX_ERR_INVALID_ARGUMENT,
+          "cfx_form_set_coefficients: a coefficient list holds at most 8 Functions (0 <= n <= 8)");
+  require(n == 0 || coeffs != nullptr, CFX_ERR_INVALID_ARGUMENT, "cfx_form_set_coefficients: null list");
+  cfx_integral_dev& I = a->integrals[integral];
+  require(user_integrand_known(I.kernel), CFX_ERR_INVALID_ARGUMENT,
+          "cfx_form_set_coefficients: a coefficient list goes with a registered integrand (the built-in kernel ids keep their "
+          "single `coefficient`)");
+  std::vector<cfx_coefficient_dev> list(n);
+  for (int k = 0; k < n; ++k)
+  {
+    const cfx_space_s* W = coeffs[k].space;
+    require(W != nullptr && coeffs[k].values != nullptr, CFX_ERR_INVALID_ARGUMENT,
+            "cfx_form_set_coefficients: every coefficient names a space and its dof values (null space or values)");
+    require(W->mesh == a->V->mesh, CFX_ERR_INVALID_ARGUMENT,
+            "cfx_form_set_coefficients: the space of a coefficient lives on another mesh than the form's");
+    list[k].space = coeffs[k].space;
+    list[k].values = to_device(coeffs[k].values, W->ndofs * W->bs); // host values: copied now; device values: aliased
+  }
+  std::swap(I.coefficients, list);
+  try
+  {
+    if (n > 0) user_coefficients_check(a, I);
+  }
+  catch (...)
+  {
+    std::swap(I.coefficients, list); // refused: the integral keeps the list it had
+    throw;
+  }
+  // the sub-forms of the complex containers (cfx_c128.hip) alias the arrays of this form's integrals
+  for (auto& kv : a->sub_forms)
+    for (size_t j = 0; j < kv.first.size(); ++j)
+    {
+      if (kv.first[j] != integral) continue;
+      std::vector<cfx_coefficient_dev>& sub = kv.second->integrals[j].coefficients;
+      sub.clear();
+      for (const cfx_coefficient_dev& c : I.coefficients)
+      {
+        sub.emplace_back();
+        sub.back().space = c.space;
+        sub.back().values.p = c.values.p; sub.back().values.n = c.values.n; sub.back().values.owned = false;
+      }
+    }
+  CFX_API_END
+}
+
 int cfx_form_destroy(cfx_form_t a)
 {
   CFX_API_BEGIN

@@ -34,9 +34,18 @@
 //                        const double* points0,         // [nq][TDIM] the facet's points in the reference cell of cell 0
 //                        const double* points1,         // ... and the SAME physical points in the reference cell of cell 1
 //                        const double* weights);        // [nq] physical (facet-measure) weights
+//
+// Coefficient lists (cfx_form_set_coefficients; the reference's Form::coefficients() packed at coefficient_offsets(),
+// pack_form.h:69-158): `w` then holds Function k of the integral's list -- CFX_W_ND<k> dofs per cell, CFX_W_BS<k>
+// components per dof, gathered through the dofmap of its own space -- at CFX_W_OFF<k> = sum_{j<k} nd_j bs_j, dof i
+// component b at CFX_W_OFF<k> + i * CFX_W_BS<k> + b, CFX_CSTRIDE doubles in all (CFX_NCOEF Functions).  Interior facets:
+// 2 CFX_CSTRIDE doubles, Function k's block of cell 0 at 2 CFX_W_OFF<k> and of cell 1 directly after it.  At most 64
+// doubles: `w` is a thread-private array the integrand indexes freely.
 #include <dlfcn.h>
 
+#include <array>
 #include <mutex>
+#include <set>
 
 #include <hip/hiprtc.h>
 
@@ -449,20 +458,71 @@ struct UserIntegrand
 {
   std::string name, source;
   int rank = 2;
-  int kind = 0;                              // 0: cell integrand, 1: interior-facet integrand
-  bool two = false;                          // a bilinear integrand between two spaces (cfx_integrand_register2)
-  std::map<int64_t, std::vector<char>> code; // variant key (variant_key) -> code object for gfx950
-  std::map<int64_t, hipModule_t> module;
-  std::map<int64_t, hipFunction_t> function;
+  int kind = 0;                                  // 0: cell integrand, 1: interior-facet integrand
+  bool two = false;                              // a bilinear integrand between two spaces (cfx_integrand_register2)
+  std::map<std::string, std::vector<char>> code; // variant key (Variant::key) -> code object for gfx950
+  std::map<std::string, hipModule_t> module;
+  std::map<std::string, hipFunction_t> function;
+  // variants with a coefficient list compiled ahead of use (cfx_integrand_compile_coefficients): once there is one, a
+  // list is launched with a variant of this set only -- the source was written for those shapes
+  std::set<std::string> declared;
 };
 
 // (tdim, dofs per cell, block size) of the form's space; nd1 > 0: (tdim, nd0, bs0) of the test space, (nd1, bs1) of the
-// trial space of a two-space integrand
+// trial space of a two-space integrand; coefs: (dofs per cell, block size) of every Function of the integral's
+// coefficient list, in order (empty: the single `coefficient`)
 struct Variant
 {
   int tdim, nd0, bs0, nd1 = 0, bs1 = 0;
-  int64_t key() const { return ((((int64_t)tdim * 100 + nd0) * 10 + bs0) * 100 + nd1) * 10 + bs1; }
+  std::vector<std::array<int, 2>> coefs;
+  int cstride() const
+  {
+    int c = 0;
+    for (const auto& k : coefs) c += k[0] * k[1];
+    return c;
+  }
+  std::string signature() const
+  {
+    std::string s;
+    for (const auto& k : coefs) s += (s.empty() ? "(" : ", (") + std::to_string(k[0]) + ", " + std::to_string(k[1]) + ")";
+    return "[" + s + "]";
+  }
+  std::string key() const
+  {
+    std::string s = std::to_string(tdim) + "/" + std::to_string(nd0) + "x" + std::to_string(bs0) + "/" + std::to_string(nd1) + "x"
+                    + std::to_string(bs1);
+    for (const auto& k : coefs) s += "/w" + std::to_string(k[0]) + "x" + std::to_string(k[1]);
+    return s;
+  }
 };
+
+// what a wrapper compiled for a coefficient list takes next to its argument struct: per Function its dof values, the
+// dofmap of its own space and its shape (the shape is compile-time in the wrapper: CFX_W_ND<k>, CFX_W_BS<k>)
+constexpr int kMaxCoefficients = 8;
+constexpr int kMaxPacked = 64; // doubles of the thread-private `w`
+struct RtcCoefArgs
+{
+  struct { const double* values; const int32_t* dofmap; int nd, bs; } c[kMaxCoefficients];
+};
+
+// the limits of a coefficient list: n Functions of (nd[k], bs[k]); `w` holds cstride doubles for a cell integral and
+// 2 cstride for an interior facet
+void check_coefficient_shapes(const char* who, bool facet, int n, const int* nd, const int* bs)
+{
+  require(n >= 0 && n <= kMaxCoefficients, CFX_ERR_INVALID_ARGUMENT,
+          (std::string(who) + ": a coefficient list holds at most 8 Functions (0 <= n <= 8)").c_str());
+  require(n == 0 || (nd && bs), CFX_ERR_INVALID_ARGUMENT, (std::string(who) + ": null argument").c_str());
+  int cstride = 0;
+  for (int k = 0; k < n; ++k)
+  {
+    require(nd[k] >= 1 && nd[k] <= 64 && bs[k] >= 1 && bs[k] <= 64, CFX_ERR_INVALID_ARGUMENT,
+            (std::string(who) + ": every coefficient has at least one dof per cell and one component").c_str());
+    cstride += nd[k] * bs[k];
+    require(cstride <= (facet ? kMaxPacked / 2 : kMaxPacked), CFX_ERR_INVALID_ARGUMENT,
+            (std::string(who) + ": the packed coefficients `w` hold at most 64 doubles per thread: cstride = sum nd_k * bs_k <= "
+             + (facet ? "32 per cell for interior facets" : "64 for cell integrals") + " (the list asks for more)").c_str());
+  }
+}
 
 std::vector<UserIntegrand>& integrands()
 {
@@ -489,17 +549,89 @@ std::string variant_defines(const Variant& v)
     d += def("CFX_ND0", std::to_string(v.nd0)) + def("CFX_BS0", std::to_string(v.bs0)) + def("CFX_NDB0", "(CFX_ND0 * CFX_BS0)")
          + def("CFX_ND1", std::to_string(v.nd1)) + def("CFX_BS1", std::to_string(v.bs1)) + def("CFX_NDB1", "(CFX_ND1 * CFX_BS1)")
          + def("CFXW_ND", "CFX_ND0") + def("CFXW_NR", "CFX_NDB0") + def("CFXW_NC", "CFX_NDB1");
+  if (!v.coefs.empty())
+  {
+    // a coefficient list: the shape and the offset in `w` of every Function (pack_form.h:69-158)
+    d += def("CFX_NCOEF", std::to_string(v.coefs.size())) + def("CFX_CSTRIDE", std::to_string(v.cstride()));
+    int off = 0;
+    for (size_t k = 0; k < v.coefs.size(); ++k)
+    {
+      const std::string ks = std::to_string(k);
+      d += def(("CFX_W_ND" + ks).c_str(), std::to_string(v.coefs[k][0])) + def(("CFX_W_BS" + ks).c_str(), std::to_string(v.coefs[k][1]))
+           + def(("CFX_W_OFF" + ks).c_str(), std::to_string(off));
+      off += v.coefs[k][0] * v.coefs[k][1];
+    }
+  }
   return d;
+}
+
+// The wrappers of a variant with a coefficient list: the texts above with the single-coefficient gather replaced by
+// the in-thread gather of the list -- every Function through the dofmap of its own space, into w[CFX_CSTRIDE] (cells) or
+// w[2 CFX_CSTRIDE] (interior facets: the block of cell 0, then of cell 1, per Function), loops over compile-time shapes.
+// The descriptors travel as a second kernel argument.  Variants without a list compile the texts above unchanged.
+std::string replace_n(std::string s, const std::string& from, const std::string& to, int times)
+{
+  int n = 0;
+  for (size_t at = s.find(from); at != std::string::npos; at = s.find(from, at + to.size()), ++n) s.replace(at, from.size(), to);
+  if (n != times) throw Error(CFX_ERR_RUNTIME, "user integrand: the stage-1 wrapper text does not hold '" + from + "'");
+  return s;
+}
+
+std::string coefficient_pack_source(const Variant& v)
+{
+  std::string s = "struct RtcCoefArgs\n{\n  struct { const double* values; const cfx_i32* dofmap; int nd, bs; } c["
+                  + std::to_string(kMaxCoefficients)
+                  + "];\n};\n"
+                    "// side s of the entity: MUL = 1 for cells, 2 for interior facets\n"
+                    "template <int MUL>\n"
+                    "__device__ __forceinline__ void cfx_pack_w(const RtcCoefArgs& CW, cfx_i64 cell, int s, double* w)\n{\n";
+  for (size_t k = 0; k < v.coefs.size(); ++k)
+  {
+    const std::string ks = std::to_string(k), nd = "CFX_W_ND" + ks, bs = "CFX_W_BS" + ks, off = "CFX_W_OFF" + ks;
+    s += "  for (int j = 0; j < " + nd + "; ++j)\n  {\n    const cfx_i64 d = CW.c[" + ks + "].dofmap[cell * " + nd + " + j];\n"
+         + "    for (int b = 0; b < " + bs + "; ++b)\n      w[MUL * " + off + " + s * (" + nd + " * " + bs + ") + j * " + bs
+         + " + b] = CW.c[" + ks + "].values[d * " + bs + " + b];\n  }\n";
+  }
+  return s + "}\n";
+}
+
+std::string wrapper_source(const UserIntegrand& u, const Variant& v)
+{
+  if (v.coefs.empty()) return u.kind == 1 ? kFacetWrapper : kWrapper;
+  std::string w;
+  if (u.kind == 1)
+  {
+    w = replace_n(kFacetWrapper, "cfx_facet_stage(const RtcFacetArgs& A)", "cfx_facet_stage(const RtcFacetArgs& A, const RtcCoefArgs& CW)", 1);
+    w = replace_n(w,
+                  "  double w[2 * CFXW_ND];\n  if (A.coeff)\n    for (int s = 0; s < 2; ++s)\n"
+                  "      for (int j = 0; j < CFXW_ND; ++j) w[s * CFXW_ND + j] = A.coeff[A.dofmap[(s ? c1 : c0) * CFXW_ND + j]];\n",
+                  "  double w[2 * CFX_CSTRIDE];\n  cfx_pack_w<2>(CW, c0, 0, w);\n  cfx_pack_w<2>(CW, c1, 1, w);\n", 1);
+    w = replace_n(w, "cfx_user_stage1(RtcFacetArgs A) { cfx_facet_stage<false>(A); }",
+                  "cfx_user_stage1(RtcFacetArgs A, RtcCoefArgs CW) { cfx_facet_stage<false>(A, CW); }", 1);
+    w = replace_n(w, "cfx_user_stage1_rules(RtcFacetArgs A) { cfx_facet_stage<true>(A); }",
+                  "cfx_user_stage1_rules(RtcFacetArgs A, RtcCoefArgs CW) { cfx_facet_stage<true>(A, CW); }", 1);
+  }
+  else
+  {
+    w = replace_n(kWrapper, "cfx_user_stage1(RtcArgs A)", "cfx_user_stage1(RtcArgs A, RtcCoefArgs CW)", 1);
+    w = replace_n(w,
+                  "  double w[CFXW_NR];\n  if (A.coeff)\n    for (int j = 0; j < CFXW_ND; ++j)\n"
+                  "      for (int b = 0; b < A.coeff_bs; ++b) w[j * A.coeff_bs + b] = A.coeff[(cfx_i64)A.dofmap[cell * CFXW_ND + j] * "
+                  "A.coeff_bs + b];\n",
+                  "  double w[CFX_CSTRIDE];\n  cfx_pack_w<1>(CW, cell, 0, w);\n", 1);
+  }
+  w = replace_n(w, "A.coeff ? w : (const double*)0", "w", 2);
+  return coefficient_pack_source(v) + w;
 }
 
 const std::vector<char>& compiled(UserIntegrand& u, const Variant& v)
 {
-  const int64_t key = v.key();
+  const std::string key = v.key();
   auto it = u.code.find(key);
   if (it != u.code.end()) return it->second;
   Rtc& r = rtc();
   const std::string src = variant_defines(v) + "#define CFX_USER_FN " + u.name + "\n" + kPrelude + "\n" + u.source + "\n"
-                          + (u.kind == 1 ? kFacetWrapper : kWrapper);
+                          + wrapper_source(u, v);
   hiprtcProgram prog = nullptr;
   if (r.create(&prog, src.c_str(), (u.name + ".hip").c_str(), 0, nullptr, nullptr) != HIPRTC_SUCCESS)
     throw Error(CFX_ERR_RUNTIME, "hiprtcCreateProgram failed");
@@ -524,7 +656,7 @@ const std::vector<char>& compiled(UserIntegrand& u, const Variant& v)
 
 hipFunction_t function_of(UserIntegrand& u, const Variant& v, bool rules = false)
 {
-  const int64_t key = v.key(), fkey = 2 * key + (rules ? 1 : 0);
+  const std::string key = v.key(), fkey = key + (rules ? "/rules" : "");
   auto it = u.function.find(fkey);
   if (it != u.function.end()) return it->second;
   auto mt = u.module.find(key);
@@ -543,7 +675,7 @@ hipFunction_t function_of(UserIntegrand& u, const Variant& v, bool rules = false
 
 // the variant a form asks of integrand u: its space, or (test, trial) when they differ; the integrand must have been
 // registered for that kind of form
-Variant form_variant(const cfx_form_s* a, const UserIntegrand& u)
+Variant form_variant(const cfx_form_s* a, const UserIntegrand& u, const cfx_integral_dev& I)
 {
   const cfx_space_s* V = a->V;
   const bool rect = a->rectangular();
@@ -553,7 +685,33 @@ Variant form_variant(const cfx_form_s* a, const UserIntegrand& u)
                  "(cfx_form_create2)");
   Variant v{V->mesh->tdim, V->ndofs_cell, V->bs};
   if (rect) { v.nd1 = a->V1->ndofs_cell; v.bs1 = a->V1->bs; }
+  for (const cfx_coefficient_dev& c : I.coefficients) v.coefs.push_back({c.space->ndofs_cell, c.space->bs});
   return v;
+}
+
+// a variant with a coefficient list about to be launched (or attached to a form): within the limits of `w`, and -- once
+// variants with a list were compiled ahead for this integrand -- one of those
+void check_list_variant(const UserIntegrand& u, const Variant& v)
+{
+  if (v.coefs.empty()) return;
+  std::vector<int> nd, bs;
+  for (const auto& k : v.coefs) { nd.push_back(k[0]); bs.push_back(k[1]); }
+  check_coefficient_shapes("cfx_form_set_coefficients", u.kind == 1, (int)nd.size(), nd.data(), bs.data());
+  require(u.declared.empty() || u.declared.count(v.key()) > 0, CFX_ERR_INVALID_ARGUMENT,
+          ("cfx_form_set_coefficients: the shapes of the coefficient list " + v.signature() + " on (tdim " + std::to_string(v.tdim)
+           + ", " + std::to_string(v.nd0) + " x " + std::to_string(v.bs0) + (v.nd1 ? ", " + std::to_string(v.nd1) + " x " + std::to_string(v.bs1) : "")
+           + ") differ from the signatures the integrand '" + u.name
+           + "' was compiled for (cfx_integrand_compile_coefficients compiles another variant)").c_str());
+}
+
+// the descriptors of the list of integral I for the wrapper
+RtcCoefArgs coefficient_args(const cfx_integral_dev& I)
+{
+  RtcCoefArgs CW{};
+  int k = 0;
+  for (const cfx_coefficient_dev& c : I.coefficients)
+    CW.c[k++] = {c.values.p, c.space->dofmap.p, c.space->ndofs_cell, c.space->bs};
+  return CW;
 }
 
 // reference rule of (dim, degree) in HBM for the wrapper (the engine's own kernels read the tables from their module)
@@ -575,9 +733,9 @@ bool user_integrand_known_locked(int kernel) { return kernel >= CFX_K_USER_BASE 
 
 // one thread per entity, 256 per block, on the library stream -- with what cfx::launch does for the engine's own
 // kernels: the launch trace, the 2^32 work-item check, HIP-event bracketing when profiling
-void module_launch(hipFunction_t fn, int64_t n, void* args)
+void module_launch(hipFunction_t fn, int64_t n, void* args, void* coef_args = nullptr)
 {
-  void* kargs[] = {args};
+  void* kargs[] = {args, coef_args}; // (a wrapper without a coefficient list takes the first alone)
   const int64_t blocks = (n + 255) / 256;
   if (blocks * 256 > 0xffffffffll) throw Error(CFX_ERR_RUNTIME, "user_integrand: launch exceeds 2^32 threads");
   const unsigned grid = (unsigned)blocks;
@@ -624,6 +782,17 @@ int user_integrand_kind(int kernel)
   return integrands()[kernel - CFX_K_USER_BASE].kind;
 }
 
+// cfx_form_set_coefficients: the list now held by integral I of form a is one its integrand can be launched with
+void user_coefficients_check(const cfx_form_s* a, const cfx_integral_dev& I)
+{
+  std::lock_guard<std::mutex> lock(rtc_mutex());
+  require(user_integrand_known_locked(I.kernel), CFX_ERR_INVALID_ARGUMENT,
+          "cfx_form_set_coefficients: a coefficient list goes with a registered integrand (the built-in kernel ids keep their "
+          "single `coefficient`)");
+  const UserIntegrand& u = integrands()[I.kernel - CFX_K_USER_BASE];
+  check_list_variant(u, form_variant(a, u, I));
+}
+
 // stage 1 of a user integrand over the standard entities (runtime = false) or the runtime rules of integral I of form a:
 // local tensors into `out` (out_mode / out_stride: see RtcArgs); `first` / `count` >= 0 restrict the launch to one entity.
 // A form between two spaces stages [NDB0][NDB1] tensors (rows: test space, columns: trial space).
@@ -637,14 +806,17 @@ void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, d
           CFX_ERR_INVALID_ARGUMENT, "user integrands serve cell integrals of Lagrange spaces of degree 1 or 2");
   UserIntegrand& u = integrands()[I.kernel - CFX_K_USER_BASE];
   require(u.kind == 0, CFX_ERR_INVALID_ARGUMENT, "this user integrand was registered for interior-facet integrals");
-  const Variant var = form_variant(a, u);
+  const Variant var = form_variant(a, u, I);
+  check_list_variant(u, var);
+  RtcCoefArgs CW = coefficient_args(I);
+  void* cw = var.coefs.empty() ? nullptr : &CW;
   require(V->ndofs_cell * V->bs <= 30 && a->V1->ndofs_cell * a->V1->bs <= 30, CFX_ERR_INVALID_ARGUMENT,
           "user integrands: at most 30 local dofs");
   RtcArgs A{};
   A.x = V->mesh->x.p; A.conn = V->mesh->conn.p; A.dofmap = V->dofmap.p;
   A.rank = a->rank; A.runtime = runtime ? 1 : 0;
   for (int k = 0; k < 8; ++k) A.params[k] = I.params[k];
-  A.coeff = I.coefficient.n > 0 ? I.coefficient.p : nullptr;
+  A.coeff = I.coefficient.n > 0 && var.coefs.empty() ? I.coefficient.p : nullptr; // (a list replaces `coefficient`)
   A.coeff_bs = a->rank == 1 ? V->bs : 1; // (as the built-in kernels pack it: cfx_fem.hip, assemble_cells_kernel)
   A.out = out; A.out_mode = out_mode; A.out_stride = out_stride;
   DevN n;
@@ -668,7 +840,7 @@ void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, d
   }
   A.n_cap = n.cap; A.n_dev = n.dev;
   if (n.cap == 0) return;
-  module_launch(function_of(u, var), n.cap, &A);
+  module_launch(function_of(u, var), n.cap, &A, cw);
 }
 
 // stage 1 of a user interior-facet integrand over the (c0, lf0, c1, lf1) rows of integral I: macro tensors
@@ -685,13 +857,16 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
           "this user integrand was registered for cell integrals (cfx_integrand_register_facet registers facet integrands)");
   require((V->degree == 1 || V->degree == 2) && (V1->degree == 1 || V1->degree == 2) && a->rank == 2, CFX_ERR_INVALID_ARGUMENT,
           "user facet integrands serve bilinear forms on Lagrange spaces of degree 1 or 2");
-  const Variant var = form_variant(a, u);
+  const Variant var = form_variant(a, u, I);
+  check_list_variant(u, var);
+  RtcCoefArgs CW = coefficient_args(I);
+  void* cw = var.coefs.empty() ? nullptr : &CW;
   require(2 * V->ndofs_cell * V->bs <= 24 && 2 * V1->ndofs_cell * V1->bs <= 24, CFX_ERR_INVALID_ARGUMENT,
           "user facet integrands: at most 24 macro dofs (scalar spaces of degree 1 or 2, vector spaces of degree 1)");
   RtcFacetArgs A{};
   A.x = V->mesh->x.p; A.conn = V->mesh->conn.p; A.dofmap = V->dofmap.p;
   for (int k = 0; k < 8; ++k) A.params[k] = I.params[k];
-  A.coeff = I.coefficient.n > 0 ? I.coefficient.p : nullptr;
+  A.coeff = I.coefficient.n > 0 && var.coefs.empty() ? I.coefficient.p : nullptr;
   RuleCopy& rc = reference_rule(var.tdim - 1, I.qdegree);
   require(rc.n <= 32, CFX_ERR_INVALID_ARGUMENT, "user facet integrand: the facet rule has more than 32 points");
   A.ref_points = rc.points.p; A.ref_weights = rc.weights.p; A.nref = rc.n;
@@ -705,7 +880,7 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
     A.n_std = INT64_MAX;
     const DevN n = only_index >= 0 ? DevN(1) : I.n_entities.devn();
     A.n_cap = n.cap; A.n_dev = n.dev;
-    if (n.cap > 0) module_launch(fn_std, n.cap, &A);
+    if (n.cap > 0) module_launch(fn_std, n.cap, &A, cw);
     return;
   }
   // [standard facets, facet-hosted rules] (exact lengths: form creation refuses a pending list next to the rules); the
@@ -719,7 +894,7 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
   {
     A.rows = I.entities.p + 4 * lo; A.out = out; A.f0 = lo;
     A.n_cap = mid - lo; A.n_dev = nullptr;
-    module_launch(fn_std, A.n_cap, &A);
+    module_launch(fn_std, A.n_cap, &A, cw);
   }
   if (hi > mid)
   {
@@ -730,7 +905,7 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
     A.scratch = scratch.p; A.scratch_stride = nq * var.tdim;
     A.rows = I.entities.p + 4 * mid; A.out = out + (mid - lo) * nt; A.f0 = mid;
     A.n_cap = hi - mid; A.n_dev = nullptr;
-    module_launch(function_of(u, var, true), A.n_cap, &A);
+    module_launch(function_of(u, var, true), A.n_cap, &A, cw);
   }
 }
 } // namespace cfx
@@ -826,6 +1001,33 @@ int cfx_integrand_compile2(int kernel_id, int tdim, int nd0, int bs0, int nd1, i
   require(u.kind == 0 || (2 * nd0 * bs0 <= 24 && 2 * nd1 * bs1 <= 24), CFX_ERR_INVALID_ARGUMENT,
           "cfx_integrand_compile2: interior-facet integrands take at most 24 macro dofs on each side");
   (void)compiled(u, Variant{tdim, nd0, bs0, nd1, bs1});
+  CFX_API_END
+}
+
+int cfx_integrand_compile_coefficients(int kernel_id, int tdim, int nd0, int bs0, int nd1, int bs1, int n, const int* nd,
+                                       const int* bs)
+{
+  CFX_API_BEGIN
+  std::lock_guard<std::mutex> lock(rtc_mutex());
+  require(user_integrand_known_locked(kernel_id), CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_compile_coefficients: unknown id");
+  UserIntegrand& u = integrands()[kernel_id - CFX_K_USER_BASE];
+  auto lagrange = [&](int m, int b) { return (m == tdim + 1 || m == (tdim + 1) * (tdim + 2) / 2) && b >= 1 && b <= 3; };
+  require((tdim == 2 || tdim == 3) && lagrange(nd0, bs0) && (nd1 == 0 || lagrange(nd1, bs1)), CFX_ERR_INVALID_ARGUMENT,
+          "cfx_integrand_compile_coefficients: tdim 2 or 3, dofs per cell of a degree-1 or degree-2 space, block size 1..3 "
+          "(nd1 = 0: a square form)");
+  require(u.two == (nd1 != 0), CFX_ERR_INVALID_ARGUMENT,
+          u.two ? "cfx_integrand_compile_coefficients: a two-space integrand names its trial space (nd1, bs1)"
+                : "cfx_integrand_compile_coefficients: the integrand was registered for square forms (nd1 = 0)");
+  require(u.kind == 0 || (2 * nd0 * bs0 <= 24 && (nd1 == 0 || 2 * nd1 * bs1 <= 24)), CFX_ERR_INVALID_ARGUMENT,
+          "cfx_integrand_compile_coefficients: interior-facet integrands take at most 24 macro dofs on each side");
+  require(n >= 1 || n > kMaxCoefficients, CFX_ERR_INVALID_ARGUMENT,
+          "cfx_integrand_compile_coefficients: a list of 1 to 8 coefficients (cfx_integrand_compile_bs / _compile2 compile the "
+          "variant without a list)");
+  check_coefficient_shapes("cfx_integrand_compile_coefficients", u.kind == 1, n, nd, bs);
+  Variant v{tdim, nd0, bs0, nd1, nd1 ? bs1 : 0};
+  for (int k = 0; k < n; ++k) v.coefs.push_back({nd[k], bs[k]});
+  (void)compiled(u, v);
+  u.declared.insert(v.key());
   CFX_API_END
 }
 

@@ -57,9 +57,17 @@ class Integral:
     params: tuple = ()
     qdegree: int = 2                          # quadrature degree on the standard entities
     coefficient: object = None                # Function / dof values of the form's space (field id F_COEFFICIENT)
+    coefficients: tuple = ()                  # registered integrands: Functions packed into `w` in this order, each on its
+                                              # own space (Form::coefficients(), pack_form.h:69-158); not with `coefficient`
     scale: complex = 1.0                      # constant that multiplies the integrand (fem.Constant kappa in `kappa * ... * dx`,
                                               # test_complex_assembly.py:55-91): a complex value makes the form complex128
     _keep: list = field(default_factory=list, repr=False)
+
+    def __post_init__(self):
+        self.coefficients = tuple(self.coefficients)
+        if self.coefficient is not None and len(self.coefficients) > 0:
+            raise ValueError("Integral: give either `coefficient` (one Function of the form's space) or `coefficients` "
+                             "(a list, each Function on its own space), not both")
 
     def _coefficient_values(self):
         return None if self.coefficient is None else getattr(self.coefficient, "values", self.coefficient)
@@ -139,6 +147,29 @@ def _f64_ptr(a, keep: list):
     return _lib.as_ptr(a, np.float64, keep)
 
 
+def _coefficient_list(functions, keep: list):
+    """(n, cfx_coefficient array) of an ordered list of Functions; what the array points to is appended to `keep`."""
+    functions = tuple(functions)
+    for f in functions:
+        if not hasattr(f, "function_space") or not hasattr(f, "values"):
+            raise TypeError("coefficients: a list of Functions (each with its function_space and values)")
+        v = f.values
+        if v.is_complex() if _lib.is_torch(v) else _is_complex(v.dtype) if isinstance(v, _lib.DeviceBuffer) else np.iscomplexobj(v):
+            raise ValueError("coefficients: complex Functions in a coefficient list are not supported (the Functions of a "
+                             "list are real; a complex constant goes into Integral.scale)")
+    arr = (_lib.Coefficient * max(len(functions), 1))()
+    for k, f in enumerate(functions):
+        W = f.function_space
+        v = f.values
+        n = v.size if isinstance(v, _lib.DeviceBuffer) else int(v.numel()) if _lib.is_torch(v) else np.asarray(v).size
+        if n != W.ndofs * W.bs:
+            raise ValueError(f"coefficients[{k}]: {n} values for a space of {W.ndofs} dofs x block size {W.bs}")
+        arr[k].space = W._h.value
+        arr[k].values = _f64_ptr(f.values, keep).value
+        keep.append(W)
+    return len(functions), arr
+
+
 class CutForm:
     """Compiled form handle (python/cutfemx/fem.py CutForm)."""
 
@@ -189,6 +220,22 @@ class CutForm:
             # the imaginary parts of the complex coefficients: a second real form, assembled with the constants i s_k
             # for the integrals that carry one and 0 for the others
             self._h_im = create("im")
+        self._coefficient_keep: dict = {}
+        for k, i in enumerate(self.integrals):
+            if len(tuple(i.coefficients)) > 0:
+                self.set_coefficients(k, i.coefficients)
+
+    def set_coefficients(self, integral_index: int, functions) -> None:
+        """Attach the ordered list of Functions `functions` to integral `integral_index` of this live form
+        (cfx_form_set_coefficients): new values or a new list, without a new form or row plan and without a host
+        read-back.  Host values are copied now, device values are aliased until they are replaced; an empty list returns
+        the integral to what it was created with.  The integrand reads Function k at `w + CFX_W_OFF<k>`."""
+        keep: list = []
+        n, arr = _coefficient_list(functions, keep)
+        handles = [self._h] + ([self._h_im] if self._h_im is not None else [])
+        for h in handles:   # (the form of the imaginary parts of a complex `coefficient` shares the real list)
+            _lib.check(_lib.lib().cfx_form_set_coefficients(h, int(integral_index), n, arr))
+        self._coefficient_keep[int(integral_index)] = keep   # (the previous list's arrays are released after the swap)
 
     def _parts(self):
         """(form handle, interleaved complex constants) of the real forms that make up this complex128 form."""
@@ -248,7 +295,25 @@ _user_integrand_rank: dict[int, int] = {}
 _user_integrand_two: set[int] = set()   # ids of cfx_integrand_register2
 
 
-def register_integrand(name: str, source: str, rank: int = 2, facet: bool = False, variant=None, trial=None) -> int:
+def _coefficient_signature(coefficients):
+    sig = [(int(c[0]), int(c[1]) if len(c) > 1 else 1) for c in coefficients]
+    nd = (C.c_int * max(len(sig), 1))(*[c[0] for c in sig])
+    bs = (C.c_int * max(len(sig), 1))(*[c[1] for c in sig])
+    return sig, nd, bs
+
+
+def _coefficient_defaults(sig) -> str:
+    """The CFX_W_* macros of the signature as defaults: the text a source is validated with where no list is compiled in."""
+    lines, off = ["#ifndef CFX_NCOEF", f"#define CFX_NCOEF {len(sig)}",
+                  f"#define CFX_CSTRIDE {sum(n * b for n, b in sig)}"], 0
+    for k, (n, b) in enumerate(sig):
+        lines += [f"#define CFX_W_ND{k} {n}", f"#define CFX_W_BS{k} {b}", f"#define CFX_W_OFF{k} {off}"]
+        off += n * b
+    return "\n".join(lines + ["#endif", ""])
+
+
+def register_integrand(name: str, source: str, rank: int = 2, facet: bool = False, variant=None, trial=None,
+                       coefficients=None) -> int:
     """Register the HIP C++ source of an integrand; returns the id to put into `Integral.kernel`.
 
     The reference generates a tabulate_tensor kernel per form at run time (runintgen / FFCx,
@@ -274,7 +339,28 @@ def register_integrand(name: str, source: str, rank: int = 2, facet: bool = Fals
     A bilinear integrand between two spaces (the off-diagonal blocks of `MixedSpace`, forms with a `trial_space`):
     `variant=(tdim, nd0, bs0, nd1, bs1)`, or `variant=(tdim, nd0[, bs0])` with `trial=(nd1[, bs1])`
     (cfx_integrand_register2).  Its tensor is [NDB0][NDB1] (cells) or [2 NDB0][2 NDB1] (interior facets), with
-    CFX_ND0 / CFX_BS0 / CFX_NDB0, CFX_ND1 / CFX_BS1 / CFX_NDB1 and cfx_tabulate0 / cfx_tabulate1 in scope."""
+    CFX_ND0 / CFX_BS0 / CFX_NDB0, CFX_ND1 / CFX_BS1 / CFX_NDB1 and cfx_tabulate0 / cfx_tabulate1 in scope.
+
+    `coefficients=[(nd_0, bs_0), (nd_1, bs_1), ...]`: the integrand reads a coefficient LIST (`Integral.coefficients`:
+    Functions on their own spaces, Function k with nd_k dofs per cell and bs_k components packed at `w + CFX_W_OFF<k>`;
+    interior facets: cell 0 at `w + 2 * CFX_W_OFF<k>`, cell 1 directly after it).  The variant with this list is compiled
+    at registration -- CFX_NCOEF, CFX_CSTRIDE, CFX_W_ND<k>, CFX_W_BS<k>, CFX_W_OFF<k> defined -- so the source is validated
+    against the signature without a GPU; a list of other shapes is then refused until `compile_integrand(...,
+    coefficients=...)` compiles its variant.  `w` holds at most 64 doubles."""
+    if coefficients is not None and len(coefficients) > 0:
+        sig, _, _ = _coefficient_signature(coefficients)
+        if variant is None:
+            variant = (3, 4, 1)
+        # the list's macros as defaults, so that the source also compiles where no list is attached
+        kid = register_integrand(name, _coefficient_defaults(sig) + source, rank, facet, variant, trial)
+        if kid in _user_integrand_two:
+            v = list(variant) + ([1] if len(variant) < 3 else [])
+            t = v[3:5] if len(v) >= 5 else (list(trial) + [1])[:2]
+            compile_integrand2(kid, v[0], v[1], v[2], t[0], t[1], coefficients=sig)
+        else:
+            tdim, nd, bs = (list(variant) + [1])[:3]
+            compile_integrand(kid, tdim, nd, bs, coefficients=sig)
+        return kid
     kid = C.c_int()
     two = trial is not None or (variant is not None and len(variant) == 5)
     if two:
@@ -306,14 +392,25 @@ def register_integrand(name: str, source: str, rank: int = 2, facet: bool = Fals
     return kid.value
 
 
-def compile_integrand(kernel_id: int, tdim: int, ndofs_cell: int, bs: int = 1) -> None:
-    """Compile the (tdim, dofs per cell, block size) variant of a registered integrand now instead of at its first use."""
+def compile_integrand(kernel_id: int, tdim: int, ndofs_cell: int, bs: int = 1, coefficients=None) -> None:
+    """Compile the (tdim, dofs per cell, block size) variant of a registered integrand now instead of at its first use;
+    `coefficients=[(nd, bs), ...]`: the variant with that coefficient list (cfx_integrand_compile_coefficients)."""
+    if coefficients is not None and len(coefficients) > 0:
+        sig, nd, cbs = _coefficient_signature(coefficients)
+        _lib.check(_lib.load().cfx_integrand_compile_coefficients(int(kernel_id), int(tdim), int(ndofs_cell), int(bs), 0, 0,
+                                                                  len(sig), nd, cbs))
+        return
     _lib.check(_lib.load().cfx_integrand_compile_bs(int(kernel_id), int(tdim), int(ndofs_cell), int(bs)))
 
 
-def compile_integrand2(kernel_id: int, tdim: int, nd0: int, bs0: int, nd1: int, bs1: int) -> None:
+def compile_integrand2(kernel_id: int, tdim: int, nd0: int, bs0: int, nd1: int, bs1: int, coefficients=None) -> None:
     """Compile the (tdim, test nd0 / bs0, trial nd1 / bs1) variant of a two-space integrand now instead of at its first
-    use (cfx_integrand_compile2)."""
+    use (cfx_integrand_compile2); `coefficients=[(nd, bs), ...]`: the variant with that coefficient list."""
+    if coefficients is not None and len(coefficients) > 0:
+        sig, nd, cbs = _coefficient_signature(coefficients)
+        _lib.check(_lib.load().cfx_integrand_compile_coefficients(int(kernel_id), int(tdim), int(nd0), int(bs0), int(nd1),
+                                                                  int(bs1), len(sig), nd, cbs))
+        return
     _lib.check(_lib.load().cfx_integrand_compile2(int(kernel_id), int(tdim), int(nd0), int(bs0), int(nd1), int(bs1)))
 
 

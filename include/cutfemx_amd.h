@@ -540,6 +540,39 @@ int cfx_integrand_compile_bs(int kernel_id, int tdim, int ndofs_cell, int bs);
 int cfx_integrand_register2(const char* name, const char* source, int facet, int tdim, int nd0, int bs0, int nd1, int bs1,
                             int* kernel_id);
 int cfx_integrand_compile2(int kernel_id, int tdim, int nd0, int bs0, int nd1, int bs1);
+/* Several coefficient Functions per integral, each on its own space -- what the reference packs for Form::coefficients()
+ * at Form::coefficient_offsets() into one array of cstride values per entity (pack_form.h:69-158).
+ *
+ * cfx_form_set_coefficients attaches an ordered list of n Functions (0 <= n <= 8) to integral `integral` of a form whose
+ * integrand is a registered one.  Each entry names a space on the form's mesh (Lagrange, degree 1 or 2, any block size
+ * 1..3) and the Function's dof values (space ndofs * bs doubles).  Host values are copied at the call; device values are
+ * aliased until they are replaced or the form is destroyed (the rule of point_data).  The call may be repeated on a live
+ * form with new values or another list -- the moving-domain loop: no new form, no new row plan, no host read-back (it
+ * never grows cfx_sync_count).  While a list is set it replaces cfx_integral.coefficient for that integral; n = 0
+ * returns the integral to what cfx_form_create gave it.
+ *
+ * Layout of `w` (the reference's, entry for entry): coefficient k, nd_k dofs per cell and bs_k components per dof, takes
+ * nd_k * bs_k doubles at off_k = sum_{j<k} nd_j * bs_j; dof i, component b at off_k + i * bs_k + b; every coefficient is
+ * gathered through its OWN space's dofmap (pack_form.h:98-106); cstride = sum_k nd_k * bs_k.  Interior facets: `w` holds
+ * 2 * cstride doubles, coefficient k's block of cell 0 at 2 * off_k and of cell 1 directly after it, at
+ * 2 * off_k + nd_k * bs_k (pack_form.h:110-131).  The single `coefficient` of a facet integrand, [2][ND], is the n = 1
+ * case.
+ *
+ * The shapes are compile-time: a variant compiled for a list defines CFX_NCOEF, CFX_CSTRIDE and, for every k,
+ * CFX_W_ND<k>, CFX_W_BS<k>, CFX_W_OFF<k> (CFX_W_OFF<k> = off_k: a facet source reads cell 0 of coefficient k at
+ * w + 2 * CFX_W_OFF<k>), next to the macros of the form's space(s).  The variant is compiled on first use, or ahead of
+ * it by cfx_integrand_compile_coefficients (nd1 = 0: a square form; no GPU needed).  A source evaluates a coefficient with
+ * cfx_tabulate_p1 / cfx_tabulate_p2.
+ *
+ * Limits (CFX_ERR_INVALID_ARGUMENT, the message names the limit): `w` is a thread-private array of at most 64 doubles --
+ * cstride <= 64 for cell integrals, cstride <= 32 per cell for interior facets; n <= 8.  Also refused: a built-in kernel
+ * id (the built-ins keep their single `coefficient`), a space on another mesh than the form's (the reference refuses
+ * codim > 0 coefficients), a null space or null values, an integral index out of range.  The complex containers
+ * (cfx_assemble_*_c128 / _c64) and the float32 ones carry the list along; the Functions themselves are real. */
+typedef struct { cfx_space_t space; const double* values; } cfx_coefficient; /* values: space ndofs * bs doubles */
+int cfx_form_set_coefficients(cfx_form_t a, int integral, int n, const cfx_coefficient* coeffs);
+int cfx_integrand_compile_coefficients(int kernel_id, int tdim, int nd0, int bs0, int nd1, int bs1, /* nd1 = 0: square */
+                                       int n, const int* nd, const int* bs);
 
 /* ---- deactivation: cpp/cutfemx/fem/deactivate.h:387-418 ------------------- */
 /* active_domain(): the two indicators (active cells, active dofs) are the marks of the form's row plan; deactivation

@@ -371,10 +371,34 @@ struct Integral
   std::span<const double> coefficient{};       // dof values of a CFX_F_COEFFICIENT field
 };
 
+/// One Function of an integral's coefficient list: its space and its dof values (ndofs * bs doubles, host or device)
+struct Coefficient
+{
+  const FunctionSpace* space = nullptr;
+  std::span<const double> values{};
+};
+
 struct Form
 {
   detail::Handle<cfx_form_t, cfx_form_destroy> handle;
   int rank = 2;
+  /// Form::coefficients() of one integral with a registered integrand (pack_form.h:69-158): the ordered list packed into
+  /// `w`, each Function through the dofmap of its own space, Function k at CFX_W_OFF<k>.  May be called again on the
+  /// live form with new values or another list (no new row plan, no host read-back); an empty list returns the
+  /// integral to what it was created with.  Host values are copied now, device values aliased until replaced.
+  void set_coefficients(int integral, std::span<const Coefficient> coefficients)
+  {
+    std::vector<cfx_coefficient> raw(coefficients.size());
+    for (std::size_t k = 0; k < coefficients.size(); ++k)
+    {
+      const Coefficient& c = coefficients[k];
+      if (c.space && (std::int64_t)c.values.size() != c.space->ndofs * c.space->bs)
+        throw std::invalid_argument("Form::set_coefficients: a coefficient has ndofs * bs values");
+      raw[k].space = c.space ? c.space->handle.h : nullptr;
+      raw[k].values = c.values.empty() ? nullptr : c.values.data();
+    }
+    check(cfx_form_set_coefficients(handle.h, integral, static_cast<int>(raw.size()), raw.data()));
+  }
   static Form create(const FunctionSpace& V, int rank, std::span<const Integral> integrals)
   {
     return create_impl(V, nullptr, rank, integrals);
