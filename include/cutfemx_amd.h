@@ -65,9 +65,13 @@ extern "C" {
 #define CFX_K_MASS 1            /* u v                                         */
 #define CFX_K_STIFFNESS 2       /* grad u . grad v                             */
 #define CFX_K_NITSCHE 3         /* -dn(u) v - dn(v) u + gamma/h u v; params[0]=gamma;
-                                   point_data = unit normals (gdim per point)  */
+                                   point_data = unit normals (gdim per point);
+                                   h = the cell's largest vertex-to-vertex distance (h_avg below = the arithmetic
+                                   mean of the two cells' h)                    */
 #define CFX_K_GHOST_GRADJUMP 4  /* gamma_g h_avg^(1 + e) [dn u][dn v]; params[0]=gamma_g, params[1]=e (0: the usual
-                                   ghost penalty; 2: the pressure term avg(h)^3 of test_assembly_stokes.py:123-131) */
+                                   ghost penalty; 2: the pressure term avg(h)^3 of test_assembly_stokes.py:123-131);
+                                   h = the cell's largest vertex-to-vertex distance, h_avg = the arithmetic mean of
+                                   the two cells' h */
 #define CFX_K_ELASTICITY 5      /* sigma(u):eps(v); params[0]=E, params[1]=nu  */
 /* extension penalty pair block, beta (v|bad - E v|root)(u|bad - E u|root) over the full bad cell
  * (cpp/cutfemx/extensions/extension_penalty.cpp:191-369): an interior-facet-TYPE integral whose
@@ -75,10 +79,13 @@ extern "C" {
  * quadrature degree on the bad cell; point_data (stride 1, one value per pair) = cellwise beta factor */
 #define CFX_K_EXTENSION_L2 8
 #define CFX_K_JUMP 9             /* interior facets: gamma / h_avg [u][v] (DG / skeleton value-jump penalty);
-                                   params[0]=gamma */
+                                   params[0]=gamma; h = the cell's largest vertex-to-vertex distance, h_avg = the
+                                   arithmetic mean of the two cells' h */
 #define CFX_K_SIP 10             /* interior facets: symmetric interior penalty of DG Poisson,
                                    -{dn u}[v] - {dn v}[u] + sigma / h_avg [u][v] (python/demo/demo_dg_poisson.py:262-265);
-                                   params[0]=sigma */
+                                   params[0]=sigma; {.} = the mean of the two cells' values, [.] = cell 0 - cell 1
+                                   along cell 0's outward normal; h = the cell's largest vertex-to-vertex distance,
+                                   h_avg = the arithmetic mean of the two cells' h */
 /* rectangular blocks (test space != trial space, cfx_form_create2): the off-diagonal blocks of Stokes and friends.
  * assemble_matrix_impl.h:68-189 takes dofmap0 / bs0 and dofmap1 / bs1 separately; invariants
  * python/tests/test_assembly_stokes.py:34-95.  CFX_K_MASS / CFX_K_STIFFNESS are also accepted there (bs0 == bs1) */

@@ -469,6 +469,8 @@ CASES = {
     "3d-n4-degenerate": (3, 4, "sphere", False, 0, (3,)),
     "2d-n7-degenerate-scrambled": (2, 7, "sphere", True, 8, (3, 6)),
     "3d-n5-gyroid": (3, 5, "gyroid", False, None, (4,)),
+    # the scrambled mesh on which the two cells of most ghost facets differ in diameter (H_CASE of the facet terms)
+    "2d-n8-sphere-scrambled": (2, 8, "sphere", True, None, (2, 4)),
 }
 
 
@@ -614,4 +616,296 @@ def exact_entries(key, cs, dofmap, bs, kind, degree, params=(), inside=None):
                 R.append(np.repeat(dofs, dofs.size)); Cc.append(np.tile(dofs, dofs.size)); Vv.append(T.ravel())
         out = (np.concatenate(R), np.concatenate(Cc), np.concatenate(Vv)) if Cc else (np.concatenate(R), np.concatenate(Vv))
         return out
-    return cached(("entries", key, kind, degree, bs, tuple(params), inside is not None), run)
+    return cached(("entries", key, kind, degree, bs, tuple(params), inside is not None,
+                   np.ascontiguousarray(dofmap, dtype=np.int64).tobytes()), run)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# facet and interface terms: Nitsche, ghost penalty, value jump, symmetric interior penalty
+# ---------------------------------------------------------------------------------------------------------------------
+# The one convention (include/cutfemx_amd.h): h of a cell is its largest vertex-to-vertex distance, h_avg of an interior
+# facet the arithmetic mean of its two cells' h.  Everything else is a polynomial integral over a whole facet, the
+# phi_h < 0 part of a facet, or the planar piece of {phi_h = 0} inside a cell.
+def _sqrt_ld(q):
+    """sqrt of a positive Fraction in longdouble."""
+    return np.sqrt(_ld(q)) if q > 0 else LD(0)
+
+
+def cell_diameter(X):
+    """Largest vertex-to-vertex distance of the simplex with vertex rows X (Fractions): the largest squared distance
+    exactly, one square root at the end."""
+    return _sqrt_ld(max(sum((a - b) ** 2 for a, b in zip(p, q)) for p, q in itertools.combinations(X, 2)))
+
+
+class Table:
+    """Moments keyed by exponent tuples (what `Moments` holds, from any source)."""
+
+    def __init__(self, m):
+        self.m = m
+
+    def table(self, A, B):
+        return np.array([[self.m[tuple(x + y for x, y in zip(a, b))] for b in B] for a in A], dtype=LD)
+
+    def scaled(self, s):
+        return Table({a: LD(s) * v for a, v in self.m.items()})
+
+
+def centroid_moments(d):
+    """The functional of the one-point rule: a rule with one point that integrates degree 1 exactly is the centroid with
+    the whole measure as weight, so its 'moment' of lambda^alpha is (1 / (d + 1))^abs(alpha)."""
+    return Table({a: _ld(F(1, (d + 1) ** sum(a))) for a in monomials(d + 1, 4)})
+
+
+def facet_match(conn, row):
+    """Vertices of the facet of an interior-facet row (c0, lf0, c1, lf1) -- those of cell 0 without the one opposite,
+    in ascending local index -- and, for either cell, the facet's index of each local vertex (None opposite the
+    facet), matched through the two connectivity rows."""
+    c0, lf0, c1, lf1 = (int(v) for v in row)
+    nv = conn.shape[1]
+    verts = [int(conn[c0, k]) for k in range(nv) if k != lf0]
+    pos = {v: i for i, v in enumerate(verts)}
+    if len(pos) != nv - 1 or int(conn[c1, lf1]) in pos or int(conn[c0, lf0]) in pos:
+        raise ValueError("not an interior-facet row")
+    maps = [tuple(None if k == lf else pos[int(conn[c, k])] for k in range(nv)) for c, lf in ((c0, lf0), (c1, lf1))]
+    return verts, maps
+
+
+@lru_cache(maxsize=None)
+def _restriction(d, degree, vmap):
+    """R[p, q] = 1 where the cell's barycentric monomial p, restricted to the facet, is the facet's monomial q: the
+    coordinate opposite the facet is 0 (a monomial that holds it vanishes), the others are the facet's own."""
+    A, Af = monomials(d + 1, degree), monomials(d, degree)
+    idx = {a: k for k, a in enumerate(Af)}
+    R = np.zeros((len(A), len(Af)), dtype=LD)
+    for p, a in enumerate(A):
+        b = [0] * d
+        for k, e in enumerate(a):
+            if e and vmap[k] is None:
+                break
+            if e:
+                b[vmap[k]] += e
+        else:
+            R[p, idx[tuple(b)]] = 1
+    return R
+
+
+class FacetBasis:
+    """The macro basis [cell 0 dofs, cell 1 dofs] on an interior facet as polynomials in the facet's barycentric
+    coordinates: values `val[s]` (nd x monomials of `degree`) and derivatives along the unit normal of cell 0
+    (-grad lambda_lf0 of cell 0, rational up to one square root) `dn[s]` (nd x monomials of degree - 1); the
+    facet's measure and the two cell diameters."""
+
+    def __init__(self, x, conn, row, degree):
+        d = conn.shape[1] - 1
+        self.d, self.degree = d, degree
+        self.verts, maps = facet_match(conn, row)
+        cells = (int(row[0]), int(row[2]))
+        Xs = [frac_rows(x[conn[c], :d]) for c in cells]
+        Gs = [gradients(X)[0] for X in Xs]
+        nvec = [-g for g in Gs[0][int(row[1])]]
+        nlen = _sqrt_ld(sum(g * g for g in nvec))
+        self.normal = np.array([_ld(g) for g in nvec], dtype=LD) / nlen
+        self.h = [cell_diameter(X) for X in Xs]
+        self.havg = (self.h[0] + self.h[1]) / 2
+        self.area = LD(measure(frac_rows(x[self.verts, :d])))
+        self.Af, self.Af1 = monomials(d, degree), monomials(d, degree - 1)
+        _, C, _, D = basis(d, degree)
+        self.val, self.dn = [], []
+        for s in range(2):
+            g = np.array([_ld(sum(a * b for a, b in zip(Gs[s][m], nvec))) for m in range(d + 1)], dtype=LD) / nlen
+            self.val.append(C @ _restriction(d, degree, maps[s]))
+            self.dn.append(np.einsum("imp,m,pq->iq", D, g, _restriction(d, degree - 1, maps[s])))
+
+    def jump(self):
+        return np.concatenate([self.val[0], -self.val[1]])
+
+    def dn_jump(self):
+        return np.concatenate([self.dn[0], -self.dn[1]])
+
+    def dn_avg(self):
+        return np.concatenate([self.dn[0], self.dn[1]]) / 2
+
+
+def facet_tensor(kind, fb, mom, params, bs=1):
+    """Local tensor of an interior-facet term over the part of the facet whose moments (normalised by the facet's
+    measure) are `mom`, in longdouble; macro dof i, component k at i * bs + k.
+    'ghost': gamma h_avg^(1 + e) [dn u][dn v], params (gamma, e); 'jump': gamma / h_avg [u][v];
+    'sip': -{dn u}[v] - {dn v}[u] + sigma / h_avg [u][v]; 'sip-penalty': the last term alone."""
+    jv, jn, an = fb.jump(), fb.dn_jump(), fb.dn_avg()
+    if kind == "ghost":
+        gamma, e = (tuple(params) + (0.0,))[:2]
+        T = LD(gamma) * fb.havg ** (1 + int(e)) * (jn @ mom.table(fb.Af1, fb.Af1) @ jn.T)
+    elif kind in ("jump", "sip-penalty"):
+        T = LD(params[0]) / fb.havg * (jv @ mom.table(fb.Af, fb.Af) @ jv.T)
+    elif kind == "sip":
+        B = jv @ mom.table(fb.Af, fb.Af1) @ an.T                  # B[i, j] = int [N_i] {dn N_j}
+        T = -B - B.T + LD(params[0]) / fb.havg * (jv @ mom.table(fb.Af, fb.Af) @ jv.T)
+    else:
+        raise ValueError(kind)
+    T = fb.area * T
+    return T if bs == 1 else np.kron(T, np.eye(bs, dtype=LD))
+
+
+def facet_dofs(fb, poly, x, conn, row, degree):
+    """Macro dof vector [cell 0, cell 1] of the functions poly[s](point) on the two cells (nodal values: vertices,
+    then edge midpoints in Basix order)."""
+    d = conn.shape[1] - 1
+    out = []
+    for s, c in enumerate((int(row[0]), int(row[2]))):
+        X = frac_rows(x[conn[c], :d])
+        pts = list(X)
+        if degree == 2:
+            pts += [[(p + q) / 2 for p, q in zip(X[a], X[b])] for a, b in EDGES[d]]
+        out += [poly[s](p) for p in pts]
+    return np.array([_ld(F(v)) for v in out], dtype=LD)
+
+
+def interior_facet_rows(conn, cells=None):
+    """All interior facets (both cells in `cells`, if given) as rows (c0, lf0, c1, lf1), c0 < c1, ascending."""
+    nv = conn.shape[1]
+    ok = None if cells is None else set(int(c) for c in cells)
+    seen = {}
+    for c in range(conn.shape[0]):
+        if ok is not None and c not in ok:
+            continue
+        for lf in range(nv):
+            seen.setdefault(tuple(sorted(int(conn[c, k]) for k in range(nv) if k != lf)), []).append((c, lf))
+    rows = sorted(v[0] + v[1] for v in seen.values() if len(v) == 2)
+    return np.array(rows, dtype=np.int32).reshape(-1, 4)
+
+
+def ghost_facets(cs):
+    """The ghost-penalty facets of `phi<0` from the inputs alone: interior facets with at least one intersected cell
+    whose other cell is intersected or inside; rows ascending.  Intersected: not all values < 0 and not all > 0."""
+    cut, inside = set(cs["cut"].tolist()), set(cs["inside"].tolist())
+    rows = interior_facet_rows(cs["conn"])
+    keep = [(r[0] in cut or r[2] in cut) and all(c in cut or c in inside for c in (r[0], r[2])) for r in rows.tolist()]
+    return rows[np.array(keep, dtype=bool)]
+
+
+def facet_phi(cs, verts):
+    return [F(float(cs["phi"][v])) for v in verts]
+
+
+def facet_moments(key, cs, fb, side=-1):
+    """Moments of the side * phi_h > 0 part of the facet, normalised by the facet's measure (clipping one dimension
+    down, as for facet hosts), cached by the facet's vertices."""
+    return cached(("fmom", key, tuple(fb.verts), side),
+                  lambda: Moments(cs["tdim"] - 1, [(facet_phi(cs, fb.verts), side)]))
+
+
+def facet_basis(key, cs, row, degree):
+    return cached(("fbasis", key, tuple(int(v) for v in row), degree), lambda: FacetBasis(cs["x"], cs["conn"], row, degree))
+
+
+class Interface:
+    """The planar piece of {phi_h = 0} inside cell c: physical surface moments of all barycentric monomials up to
+    degree 4, the unit normal (with the recorded floor), the cell's diameter and lambda gradients."""
+
+    def __init__(self, cs, c):
+        d = cs["tdim"]
+        X = frac_rows(cs["x"][cs["conn"][c], :d])
+        phi = cell_phi(cs.get("phis", [cs["phi"]]), cs["conn"][c])[0]
+        al = monomials(d + 1, 4)
+        self.d = d
+        self.mom = Table({a: LD(v) for a, v in zip(al, interface_moments(d, phi, X, al, 4))})
+        self.normal = np.array(normal(phi, X), dtype=LD)
+        self.h = cell_diameter(X)
+        self.G, _ = cell_geometry(cs["x"][cs["conn"][c], :d])
+        # the same term with the whole cell's normalised moments times h^(tdim - 1) in place of the surface's: its scale
+        self.whole = Table({a: _ld(whole_moment(d, a)) for a in al}).scaled(self.h ** (d - 1))
+
+
+def interface(key, cs, c):
+    return cached(("itf-cell", key, int(c)), lambda: Interface(cs, c))
+
+
+def nitsche(itf, degree, gamma, mom=None):
+    """-dn(u) v - dn(v) u + gamma / h u v over the interface piece (longdouble)."""
+    mom = itf.mom if mom is None else mom
+    A, C, A1, D = basis(itf.d, degree)
+    Dn = np.einsum("imp,m->ip", D, itf.G @ itf.normal)
+    B = C @ mom.table(A, A1) @ Dn.T                               # B[i, j] = int N_i dn N_j
+    return -B - B.T + LD(gamma) / itf.h * (C @ mom.table(A, A) @ C.T)
+
+
+def nitsche_rhs(itf, degree, gamma, scale=1.0, mom=None):
+    """-dn(v) g + gamma / h g v with the constant datum g = scale."""
+    mom = itf.mom if mom is None else mom
+    A, C, A1, D = basis(itf.d, degree)
+    Dn = np.einsum("imp,m->ip", D, itf.G @ itf.normal)
+    one = [tuple([0] * (itf.d + 1))]
+    return LD(scale) * (-(Dn @ mom.table(A1, one))[:, 0] + LD(gamma) / itf.h * (C @ mom.table(A, one))[:, 0])
+
+
+def _blocked(dofs, bs):
+    return (np.asarray(dofs, dtype=np.int64)[:, None] * bs + np.arange(bs)[None, :]).ravel()
+
+
+def exact_facet_entries(key, cs, dofmap, bs, kind, degree, params, rows, cut_rows=(), one_point=False):
+    """COO entries of an interior-facet term over the whole facets `rows` and the phi<0 parts of `cut_rows`, scattered
+    with the blocked dofmap of the two cells.  one_point: the value of the one-point rule instead of the integral."""
+    d = cs["tdim"]
+    whole = centroid_moments(d - 1) if one_point else Moments(d - 1)
+
+    def run():
+        R, Cc, Vv = [], [], []
+        for part, rr in ((False, rows), (True, cut_rows)):
+            for row in np.asarray(rr).reshape(-1, 4):
+                fb = facet_basis(key, cs, row, degree)
+                T = facet_tensor(kind, fb, facet_moments(key, cs, fb) if part else whole, params, bs).astype(np.float64)
+                dofs = _blocked(np.concatenate([dofmap[row[0]], dofmap[row[2]]]), bs)
+                R.append(np.repeat(dofs, dofs.size)); Cc.append(np.tile(dofs, dofs.size)); Vv.append(T.ravel())
+        return np.concatenate(R), np.concatenate(Cc), np.concatenate(Vv)
+    tag = tuple(np.ascontiguousarray(a, dtype=np.int64).tobytes() for a in (rows, cut_rows, dofmap))
+    return cached(("fentries", key, kind, degree, bs, tuple(params), one_point, tag), run)
+
+
+def exact_nitsche_entries(key, cs, dofmap, degree, gamma, rhs_scale=None):
+    """COO entries of the Nitsche matrix (rhs_scale None) or of the g = rhs_scale Nitsche vector over the kept cut
+    cells (`keep_itf`)."""
+    def run():
+        R, Cc, Vv = [], [], []
+        for c in cs["cut"][cs["keep_itf"]]:
+            itf = interface(key, cs, c)
+            dofs = np.asarray(dofmap[c], dtype=np.int64)
+            if rhs_scale is None:
+                T = nitsche(itf, degree, gamma).astype(np.float64)
+                R.append(np.repeat(dofs, dofs.size)); Cc.append(np.tile(dofs, dofs.size)); Vv.append(T.ravel())
+            else:
+                R.append(dofs); Vv.append(nitsche_rhs(itf, degree, gamma, rhs_scale).astype(np.float64))
+        return (np.concatenate(R), np.concatenate(Cc), np.concatenate(Vv)) if Cc else (np.concatenate(R), np.concatenate(Vv))
+    return cached(("nentries", key, degree, gamma, rhs_scale, np.ascontiguousarray(dofmap, dtype=np.int64).tobytes()), run)
+
+
+# ---- the facet cases ---------------------------------------------------------------------------------------------------
+# On the generated Kuhn boxes every cell has the same diameter, so h0, h1, (h0 + h1) / 2 and max(h0, h1) agree there;
+# only a scrambled mesh tells them apart.  H_CASE is the one on which abs(h0 - h1) > 0.05 h_avg holds on more than half
+# of the ghost facets (asserted from the inputs).  In 3-D the six tetrahedra of a Kuhn cube share its body diagonal, which
+# stays their longest edge after the scramble, so at most the facets between two cubes -- half of all -- can differ and
+# about a quarter do by more than 5 %: the 3-D scrambled case is compared as well, the assertion is made on H_CASE.
+FACET_CASES = ["2d-n8-sphere", "3d-n4-sphere", "3d-n4-sphere-scrambled", "2d-n7-degenerate-scrambled", "2d-n8-sphere-scrambled"]
+H_CASE = "2d-n8-sphere-scrambled"
+
+
+def facet_case(O, name):
+    """Facet entities of a case from its inputs alone.  ghost: rows; skeleton: all interior facets, the ones inside
+    (every facet vertex < 0: whole facets), the cut ones (neither all < 0 nor all > 0: phi<0 parts); `*_keep`: what
+    is compared -- not facets whose vertex values are all exactly zero (as `host_case`), nor facets both of whose
+    cells are all-zero cells; h: (h0, h1) of every ghost facet."""
+    def run():
+        cs = build_case(O, name)
+        conn, phi = cs["conn"], cs["phi"]
+        allzero = np.all(phi[conn] == 0, axis=1)
+        rows = interior_facet_rows(conn)
+        v = phi[host_vertices(conn, rows)]
+        neg, pos = np.all(v < 0, axis=1), np.all(v > 0, axis=1)
+        both0 = allzero[rows[:, 0]] & allzero[rows[:, 2]]
+        ghost = ghost_facets(cs)
+        cutset = set(cs["cut"].tolist())
+        kinds = np.array([(r[0] in cutset) + (r[2] in cutset) for r in ghost.tolist()])
+        h = np.array([[float(cell_diameter(frac_rows(cs["x"][conn[c], :cs["tdim"]]))) for c in (r[0], r[2])] for r in ghost])
+        return dict(rows=rows, inside=rows[neg], cut=rows[~neg & ~pos], cut_keep=(~np.all(v == 0, axis=1) & ~both0)[~neg & ~pos],
+                    inside_keep=~both0[neg], ghost=ghost, ghost_keep=~(allzero[ghost[:, 0]] & allzero[ghost[:, 2]]),
+                    n_cut_cut=int((kinds == 2).sum()), n_cut_inside=int((kinds == 1).sum()), h=h)
+    return cached(("facets", name), run)
