@@ -643,6 +643,23 @@ struct Stencil
   DevArray<uint16_t> st_loc;
   bool tiles_built = false, tiles_usable = false;
   int max_tile_verts = 0, max_tile_items = 0, max_tile_st = 0; // items: dof->cells entries, st: neighbour entries
+  // Lattice rows (cfx::space_lattice, built on first use): rows whose incident cells are bitwise translates of the
+  // cells of one representative row lat_rstar -- the same slot4 words and the same fl(x_o - x_r) for every stencil
+  // position, compared as 64-bit integers.  Such a row of an uncut inline stiffness integral is the same lat_len
+  // numbers as lat_rstar's (p1_stiffness_row works from the differences only) and is copied from lat_tmpl, the row the
+  // ordered tile kernel computes for lat_rstar (cfx::lattice_template, first use).  The flag is bit 7 of diagpos
+  // (kLatFlag; positions are below 64): every reader of diagpos masks it off.  lat_rows = 0: no flag is set.
+  bool lat_built = false, lat_tmpl_built = false;
+  int64_t lat_rows = 0, lat_rstar = -1;
+  int64_t lat_sb0 = 0;  // stencil offset of the first row of lat_rstar's tile
+  int lat_rel = 0;      // lat_rstar's segment in its tile's stencil range
+  int lat_len = 0;      // its stencil length
+  DevArray<double> lat_scratch;               // the tile of lat_rstar as the ordered tile kernel wrote it
+  const double* lat_tmpl = nullptr;           // = lat_scratch + lat_rel
+  // Rows written from the template so far, the passes of void steps included.  Diagnostics only (the tests' "path
+  // taken", cfx_space_lattice_rows): nothing in the assembly reads it.  It costs the streaming role one global atomic
+  // per block and launch (at most 4096).
+  DevArray<unsigned long long> lat_written;
   // The single-pass build of the neighbour lists stages 64 columns per dof (34 GB at 512^3).  Giving that block back to
   // the driver made the NEXT large hipMalloc of the process take 1.5 - 2.6 s on this stack (tools/time_malloc.py: 0.2 ms
   // for the first 34 GB, 1.8 s for the same request after a hipFree of 34 GB); left in the block cache it would sit
@@ -666,6 +683,16 @@ struct Stencil
   }
 };
 constexpr int kRowTile = 16;
+constexpr unsigned kLatFlag = 0x80u, kDiagPosMask = 0x7fu; // Stencil::diagpos: lattice flag | position
+// A plain row that is copied from the lattice template: flagged, all its cells in exactly one of the inline integrals
+// `inline_bits`, its whole stencil present (`full` = the lat_len low bits).  The ONE statement of the rule: the streaming
+// role that writes such rows, the tile role that leaves them out and the filtered tile list (LatTileStart) must agree
+// row for row, or a row is written twice or never.
+__device__ __forceinline__ bool lattice_template_row(unsigned diagpos_raw, unsigned umark, unsigned long long mask,
+                                                     unsigned inline_bits, unsigned long long full)
+{
+  return (diagpos_raw & kLatFlag) != 0 && __popc(umark & inline_bits) == 1 && mask == full;
+}
 
 // Cell blocks of a space (mesh-static, built on first use by cfx::space_vec_blocks): B consecutive cells and the
 // sorted union of their dofs.  A linear form's element vectors are summed per (block, dof) in LDS and leave the
@@ -898,6 +925,12 @@ struct cfx_row_plan
   // positions in plain_rows where a new row tile (dof id / kRowTile) starts: the work list of the tile kernels
   cfx::DevArray<int32_t> plain_tile_first, plain_tile_id; // ... and the tile's number
   cfx::Count n_plain_tiles;
+  // the same list without the tiles whose plain rows all take the lattice template (Stencil::lat_tmpl) for the inline
+  // integrals `lat_bits`: first = position of the tile's first plain row that does not (cfx::plain_lattice_tiles)
+  cfx::DevArray<int32_t> lat_tile_first, lat_tile_id;
+  cfx::Count n_lat_tiles;
+  bool lat_tiles_built = false;
+  unsigned lat_bits = 0;
   // linear forms, P1: the element vectors of the uncut cells are staged in the order the plain rows read them
   // (cfx::plain_vec_offsets): entry k of plain row r lives at vec_t2off[r] - 1 + k, k = position of the cell in the
   // row's dof->cells list.  vec_t2off[dof] = 0 off the plain rows (offsets are stored + 1).  vec_fast: -1 not decided, 0 no, 1 yes
@@ -983,6 +1016,9 @@ const Stencil& space_stencil_slotn(cfx_space_s* V);                     // cfx_r
 bool plain_row_masks(cfx_form_s* a, int32_t* counts = nullptr, int* maxlen = nullptr); // cfx_rowasm.hip
 void plan_cut_cells(cfx_form_s* a);                                     // cfx_rowasm.hip
 const Stencil& space_stencil_tiles(cfx_space_s* V);                     // cfx_rowasm.hip
+const Stencil& space_lattice(cfx_space_s* V);                           // cfx_rowasm.hip (Stencil::lat_rows)
+bool lattice_template(cfx_space_s* V);                                  // cfx_gather.hip (Stencil::lat_tmpl)
+bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits);          // cfx_rowasm.hip (cfx_row_plan::lat_tile_first)
 bool space_dof_verts(cfx_space_s* V);                                   // cfx_rowasm.hip (cfx_space_s::dof_verts)
 bool plain_vec_offsets(cfx_form_s* L, uint8_t mark);                    // cfx_rowasm.hip
 bool source_groups_ok(cfx_form_s* L, uint8_t mark);                     // cfx_gather.hip

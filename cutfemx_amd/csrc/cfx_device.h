@@ -387,6 +387,101 @@ inline Count compact_count(const char* name, const char* site, DevN n, Pred pred
   return total;
 }
 
+// Two compactions of the same index range in the passes of one: the per-tile counts travel packed (A | B << 32, both
+// below 2^31: positions are int32), one scan, one write pass (inside a step: one chained launch).  emit as above.
+template <typename PredA, typename PredB>
+__global__ void __launch_bounds__(kBlock) compact_count2_n_kernel(DevN n_d, PredA pa, PredB pb, int64_t* tile_counts)
+{
+  const int64_t n = dev_n(n_d);
+  const int64_t base = (int64_t)blockIdx.x * kTile;
+  int64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k)
+  {
+    const int64_t i = base + (int64_t)k * kBlock + threadIdx.x;
+    if (i < n) c += (pa(i) ? 1ll : 0ll) + (pb(i) ? (1ll << 32) : 0ll);
+  }
+  int64_t total;
+  (void)block_exclusive_scan<int64_t>(c, total);
+  if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
+}
+
+template <typename PredA, typename PredB, typename EmitA, typename EmitB>
+__global__ void __launch_bounds__(kBlock) compact_write2_n_kernel(DevN n_d, PredA pa, PredB pb, EmitA ea, EmitB eb,
+                                                                  const int64_t* tile_offsets, int32_t* outA, int64_t capA,
+                                                                  int32_t* outB, int64_t capB, ChainState chain,
+                                                                  int64_t* __restrict__ total_out, CountJobs after)
+{
+  // chain.state: count + offsets + write in this one launch (compact_chained_kernel); else offsets from the scan
+  const int64_t n = dev_n(n_d);
+  const unsigned int tile = chain.state ? chain_take_tile(chain.ticket) : blockIdx.x;
+  const int64_t base = (int64_t)tile * kTile + (int64_t)threadIdx.x * kScanItems;
+  bool fa[kScanItems], fb[kScanItems];
+  int64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k)
+  {
+    const int64_t i = base + k;
+    fa[k] = (i < n) && pa(i);
+    fb[k] = (i < n) && pb(i);
+    c += (fa[k] ? 1ll : 0ll) + (fb[k] ? (1ll << 32) : 0ll);
+  }
+  int64_t total;
+  const int64_t off = block_exclusive_scan<int64_t>(c, total);
+  int64_t prefix;
+  if (chain.state) prefix = (int64_t)chain_exclusive_prefix(chain.state, tile, (unsigned long long)total);
+  else prefix = tile_offsets[tile];
+  int64_t oa = ((prefix + off) & 0xffffffffll), ob = ((prefix + off) >> 32);
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k)
+  {
+    if (fa[k]) { if (oa < capA) { outA[oa] = (int32_t)(base + k); ea(oa, base + k); } ++oa; }
+    if (fb[k]) { if (ob < capB) { outB[ob] = (int32_t)(base + k); eb(ob, base + k); } ++ob; }
+  }
+  if (chain.state && tile == gridDim.x - 1 && threadIdx.x == kBlock - 1)
+  {
+    *total_out = prefix + total;
+    if (after.n > 0) count_publish(after);
+  }
+}
+
+// `pre(capA, capB)`: called once the capacities are known and before the write pass
+template <typename PredA, typename PredB, typename EmitA, typename EmitB>
+inline void compact_count_pair(const char* name, const char* const sites[2], DevN n, PredA pa, PredB pb, EmitA& ea, EmitB& eb,
+                               DevArray<int32_t>& outA, DevArray<int32_t>& outB, Count totals[2],
+                               const std::function<void(int64_t, int64_t)>& pre)
+{
+  const int64_t ntiles = (n.cap + kTile - 1) / kTile;
+  if (ntiles == 0)
+  {
+    outA.alloc(0); outB.alloc(0);
+    step_record(sites[0], 0); step_record(sites[1], 0);
+    totals[0] = Count(0); totals[1] = Count(0);
+    pre(0, 0);
+    return;
+  }
+  DevArray<int64_t> counts;
+  DevArray<int64_t> offsets(ntiles + 1);
+  const CountSource src[2] = {{offsets.p + ntiles, kCountLo32, kCountUpTo}, {offsets.p + ntiles, kCountHi32, kCountUpTo}};
+  CountPlan cp(2, sites, src);
+  const ChainState chain = fused_chain(cp.publish, ntiles);
+  CountJobs after{};
+  if (chain.state) after = cp.take_jobs();
+  else
+  {
+    counts.alloc(ntiles);
+    launch(name, compact_count2_n_kernel<PredA, PredB>, dim3((unsigned)ntiles), dim3(kBlock), 0, n, pa, pb, counts.p);
+    exclusive_scan(counts.p, offsets.p, ntiles, &cp);
+  }
+  cp.finish(totals);
+  outA.alloc(totals[0].cap()); outB.alloc(totals[1].cap());
+  if (totals[0].cell) outA.count = totals[0];
+  if (totals[1].cell) outB.count = totals[1];
+  pre(totals[0].cap(), totals[1].cap());
+  launch(name, compact_write2_n_kernel<PredA, PredB, EmitA, EmitB>, dim3((unsigned)ntiles), dim3(kBlock), 0, n, pa, pb, ea, eb,
+         offsets.p, outA.p, totals[0].cap(), outB.p, totals[1].cap(), chain, offsets.p + ntiles, after);
+}
+
 // ---------------------------------------------------------------------------
 // compaction of a byte array (classification codes, flags): 16 B per lane per
 // load, so a wave streams 1 KiB per instruction instead of 64 B.

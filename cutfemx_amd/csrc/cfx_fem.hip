@@ -1889,6 +1889,19 @@ int cfx_space_static_bytes(cfx_space_t V, int64_t bytes[4])
   CFX_API_END
 }
 
+int cfx_space_lattice_rows(cfx_space_t V, int64_t* n, int64_t* template_rows)
+{
+  CFX_API_BEGIN
+  require(V && n, CFX_ERR_INVALID_ARGUMENT, "cfx_space_lattice_rows: null argument");
+  *n = 0;
+  if (template_rows) *template_rows = 0;
+  if (V->degree != 1 || V->bs != 1 || !cfx::space_stencil(V).usable) return CFX_OK;
+  const cfx::Stencil& S = cfx::space_lattice(V);
+  *n = S.lat_rows;
+  if (template_rows && S.lat_rows > 0 && S.lat_written.p) *template_rows = (int64_t)cfx::read_scalar(S.lat_written.p);
+  CFX_API_END
+}
+
 int cfx_space_destroy(cfx_space_t V)
 {
   CFX_API_BEGIN

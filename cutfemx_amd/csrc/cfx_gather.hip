@@ -42,16 +42,16 @@ constexpr int kWave = 64;
 #ifndef CFX_XCD_TILE
 #define CFX_XCD_TILE 128 // measured at 512^3: vector gather -7 %, matrix kernels -2 %; 8192 (one chunk per XCD) +5 %
 #endif
-__device__ __forceinline__ int64_t row_block_id()
+__device__ __forceinline__ int64_t row_block_id(int64_t b)
 {
 #if CFX_XCD_TILE > 0
   constexpr int64_t T = CFX_XCD_TILE;
-  const int64_t b = blockIdx.x;
   return (b / (8 * T)) * (8 * T) + (b % 8) * T + (b / 8) % T;
 #else
-  return blockIdx.x;
+  return b;
 #endif
 }
+__device__ __forceinline__ int64_t row_block_id() { return row_block_id(blockIdx.x); }
 #ifndef CFX_ROW_BLOCK
 #define CFX_ROW_BLOCK row_block_id()
 #endif
@@ -2129,7 +2129,7 @@ __global__ void __launch_bounds__(kWave, CFX_PLAIN_WAVES) assemble_rows_plain_ke
   }
   const int64_t cb = live ? A.d2c_off[r] : 0;
   const int nc = (live && len > 0) ? (int)(A.d2c_off[r + 1] - cb) : 0;
-  const unsigned dpos = live ? A.diagpos[r] : 0u;
+  const unsigned dpos = live ? (A.diagpos[r] & kDiagPosMask) : 0u;
   const bool row_bc = live && A.bc0 && A.bc0[r];
   const bool diag_bc = row_bc || (live && A.bc1 != nullptr && A.bc1[r] != 0);
   double xr[TDIM];
@@ -2366,7 +2366,21 @@ struct TileArgs
   int fresh;
   int* error;
   int64_t ndofs;
+  // lattice rows (Stencil::lat_tmpl; lat_len = 0: none): the first `stream_blocks` blocks write the plain rows that
+  // take the template, the others run the tiles of tile_first / tile_id, in which such rows are not live
+  int lat_len;
+  unsigned stream_blocks; // a multiple of 8: the tile blocks keep their XCD
+  const double* lat_tmpl;
+  unsigned long long* lat_written;
 };
+
+// a plain row that is lat_len copied numbers (lattice_template_row; no boundary marks: the host sets lat_len = 0 for a
+// form that has them)
+__device__ __forceinline__ bool lattice_row(unsigned diagpos_raw, uint8_t umark, unsigned long long mask, unsigned inline_bits,
+                                            int lat_len)
+{
+  return lat_len > 0 && lattice_template_row(diagpos_raw, umark, mask, inline_bits, (1ull << lat_len) - 1ull);
+}
 
 // LDS capacity classes of a tile (vertices of the union, neighbour entries, dof->cells entries).  The arrays are
 // separate __shared__ objects so that the compiler knows the accumulator atomics cannot alias the staged tables
@@ -2410,7 +2424,54 @@ __global__ void __launch_bounds__(kWave, CFX_TILE_WAVES) assemble_tiles_plain_ke
   __shared__ uint32_t s_s4[CAPI];
   __shared__ uint16_t s_loc[CAPS];
   const int lane = threadIdx.x, g = lane / G, gl = lane % G;
-  const int64_t w = CFX_ROW_BLOCK;
+  if (blockIdx.x < A.stream_blocks)
+  {
+    // ---- streaming role: 64 plain rows per pass; the rows that take the template are ranked, their CSR offsets
+    // staged in LDS, and the lanes run over the lat_len * (rows) values -- consecutive rows are one contiguous span
+    const int64_t n_plain = dev_n(A.n_plain);
+    const int L = A.lat_len;
+    const unsigned long long fullmask = (1ull << L) - 1ull;
+    if (lane < L) s_val[kWave + lane] = A.lat_tmpl[lane];
+    unsigned long long written = 0;
+    for (int64_t c = blockIdx.x; c * kWave < n_plain; c += A.stream_blocks)
+    {
+      const int64_t i = c * kWave + lane;
+      bool take = false;
+      int64_t rbs = 0;
+      if (i < n_plain)
+      {
+        const int32_t rw = A.rows[i];
+        take = lattice_template_row(A.diagpos[rw], A.uniform[i], A.masks[i], A.inline_bits, fullmask);
+        if (take) rbs = A.indptr[rw];
+      }
+      const unsigned long long tk = __ballot(take);
+      const int ntake = __popcll(tk);
+      if (take) s_val[__popcll(tk & ((1ull << lane) - 1ull))] = __longlong_as_double(rbs);
+      __syncthreads();
+      const unsigned total = (unsigned)(ntake * L);
+      if (A.fresh)
+      {
+        for (unsigned e = lane; e < total; e += kWave)
+        {
+          const unsigned j = e / (unsigned)L, k = e - j * (unsigned)L;
+          A.values[__double_as_longlong(s_val[j]) + k] = s_val[kWave + k];
+        }
+      }
+      else
+      {
+        for (unsigned e = lane; e < total; e += kWave)
+        {
+          const unsigned j = e / (unsigned)L, k = e - j * (unsigned)L;
+          A.values[__double_as_longlong(s_val[j]) + k] += s_val[kWave + k];
+        }
+      }
+      written += (unsigned long long)ntake;
+      __syncthreads();
+    }
+    if (lane == 0 && written) atomicAdd(A.lat_written, written);
+    return;
+  }
+  const int64_t w = row_block_id((int64_t)blockIdx.x - A.stream_blocks);
   if (w >= dev_n(A.n_tiles)) return;
   const int64_t i0 = A.tile_first[w];
   const int64_t t = A.tile_id[w];
@@ -2428,15 +2489,17 @@ __global__ void __launch_bounds__(kWave, CFX_TILE_WAVES) assemble_tiles_plain_ke
   const int64_t r = r0 + g;
   const int64_t rq = r < A.ndofs ? r : A.ndofs - 1;
   const int64_t rb = A.indptr[rq], re = A.indptr[rq + 1];
-  const unsigned dpos = A.diagpos[rq];
+  const unsigned dpos_raw = A.diagpos[rq];
+  const unsigned dpos = dpos_raw & kDiagPosMask;
   // which rows of the tile are plain: their ids are the next entries of the (ascending) plain list
   unsigned pm = (rl >= 0 && rl / kRowTile == t) ? 1u << (rl % kRowTile) : 0u;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) pm |= __shfl_xor(pm, o, 64);
-  const bool live = (pm >> g) & 1u;
+  const bool plain = (pm >> g) & 1u;
   const int64_t pi = i0 + __popc(pm & ((1u << g) - 1u));
-  const unsigned long long mask = live ? A.masks[pi] : 0ull;
-  const uint8_t umark = live ? A.uniform[pi] : (uint8_t)0;
+  const unsigned long long mask = plain ? A.masks[pi] : 0ull;
+  const uint8_t umark = plain ? A.uniform[pi] : (uint8_t)0;
+  const bool live = plain && !lattice_row(dpos_raw, umark, mask, A.inline_bits, A.lat_len); // (those: the streaming role)
   const int64_t sb0 = __shfl(so, 0, 64), cb0 = __shfl(co, 0, 64);
   const int nst = (int)(__shfl(so, kRowTile, 64) - sb0), nit = (int)(__shfl(co, kRowTile, 64) - cb0);
   const int st_rel = (int)(__shfl(so, g, 64) - sb0);
@@ -2989,7 +3052,7 @@ __global__ void __launch_bounds__(kWave) assemble_vec_rows_kernel(RowArgs A)
   const int64_t cb = live ? A.d2c_off[r] : 0;
   const int nc = live ? (int)(A.d2c_off[r + 1] - cb) : 0;
   double part = 0.0; // items gl, gl+G, ... in ascending order
-  const unsigned dpos = (live && A.slot4) ? A.diagpos[r] : 0u;
+  const unsigned dpos = (live && A.slot4) ? (A.diagpos[r] & kDiagPosMask) : 0u;
   constexpr int R = G <= 4 ? 6 : 4;
   for (int base = 0;; base += R * G)
   {
@@ -4198,7 +4261,20 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
             T.tile_voff = stt.tile_voff.p; T.tile_verts = stt.tile_verts.p;
             T.indptr = Q.indptr; T.values = Q.values; T.bc0 = Q.bc0; T.bc1 = Q.bc1;
             T.inline_bits = inline_bits; T.fresh = Q.fresh; T.error = Q.error; T.ndofs = a->V->ndofs;
-            const dim3 gt = row_grid(plan.n_plain_tiles.cap());
+            int64_t tile_blocks = plan.n_plain_tiles.cap();
+            // lattice rows: written from the template by the first blocks of the launch; the tile role then runs the
+            // tiles that hold another plain row (plan.lat_tile_first)
+            if (!bc0 && !bc1 && lattice_template(a->V) && plain_lattice_tiles(a, inline_bits))
+            {
+              T.lat_len = stn.lat_len; T.lat_tmpl = stn.lat_tmpl; T.lat_written = stn.lat_written.p;
+              T.n_tiles = plan.n_lat_tiles; T.tile_first = plan.lat_tile_first.p; T.tile_id = plan.lat_tile_id.p;
+              tile_blocks = plan.n_lat_tiles.cap();
+              // >= 256 rows per wavefront, at most 16 wavefronts per CU in flight
+              const int64_t chunks = (plan.n_plain_rows.cap() + kWave - 1) / kWave;
+              T.stream_blocks = (unsigned)((std::min<int64_t>(std::max<int64_t>(chunks / 4, 1), 4096) + 7) / 8 * 8);
+            }
+            const dim3 gt = T.stream_blocks ? dim3(T.stream_blocks + (tile_blocks > 0 ? row_grid(tile_blocks).x : 0u))
+                                            : row_grid(tile_blocks);
             if (tcls == 0)
             {
               if (det) launch("assemble_tiles_plain", assemble_tiles_plain_kernel<TDIM, true, 0>, gt, dim3(kWave), 0, T);
@@ -4698,8 +4774,74 @@ void run_vector(cfx_form_s* L, double* b)
 
 } // namespace
 
+namespace
+{
+// the rows of one tile as an all-plain list: every row holds its whole stencil, all its cells carry mark 1
+__global__ void __launch_bounds__(kWave) lattice_tile_rows_kernel(int64_t t, int64_t ndofs, const int64_t* __restrict__ st_off,
+                                                                  int32_t* __restrict__ rows, unsigned long long* __restrict__ masks,
+                                                                  uint8_t* __restrict__ uniform, int32_t* __restrict__ first_id)
+{
+  const int lane = threadIdx.x;
+  const int64_t r = t * kRowTile + lane;
+  if (lane < kRowTile && r < ndofs)
+  {
+    const int len = (int)(st_off[r + 1] - st_off[r]);
+    rows[lane] = (int32_t)r;
+    masks[lane] = len >= 64 ? ~0ull : (1ull << len) - 1ull;
+    uniform[lane] = 1;
+  }
+  if (lane == 0) { first_id[0] = 0; first_id[1] = (int32_t)t; }
+}
+} // namespace
+
 namespace cfx
 {
+
+// The template of the lattice rows: the tile of the representative row run through the ORDERED tile kernel with every
+// cell marked for one inline integral, into a scratch row block laid out like the stencil.  In deterministic mode the
+// copy is therefore bit for bit what that kernel writes for any flagged row (equal differences, equal item order).
+bool lattice_template(cfx_space_s* V)
+{
+  Stencil& S = const_cast<Stencil&>(space_lattice(V));
+  if (S.lat_rows <= 0) return false;
+  if (S.lat_tmpl_built) return S.lat_tmpl != nullptr;
+  const int tcls = tile_class(S);
+  const int tdim = V->mesh->tdim;
+  if (tcls < 0 || (tdim != 2 && tdim != 3)) { S.lat_tmpl_built = true; return false; }
+  const Adjacency& adj = V->dof_cells();
+  const int64_t t = S.lat_rstar / kRowTile;
+  const int64_t nrows = std::min<int64_t>(kRowTile, V->ndofs - t * kRowTile);
+  DevArray<int32_t> rows(kRowTile), first_id(2);
+  DevArray<unsigned long long> masks(kRowTile);
+  DevArray<uint8_t> uniform(kRowTile);
+  ZeroFlag err;
+  S.lat_scratch.alloc(std::max(S.max_tile_st, 1));
+  S.lat_scratch.zero();
+  launch("lattice_template", lattice_tile_rows_kernel, dim3(1), dim3(kWave), 0, t, V->ndofs, S.offsets.p, rows.p, masks.p,
+         uniform.p, first_id.p);
+  TileArgs T{};
+  T.x = V->mesh->x.p; T.n_tiles = DevN(1); T.tile_first = first_id.p; T.tile_id = first_id.p + 1;
+  T.n_plain = DevN(nrows); T.rows = rows.p; T.masks = masks.p; T.uniform = uniform.p;
+  T.d2c_off = adj.offsets.p; T.d2c = adj.cells.p; T.slot4 = S.slot4.p; T.cellmark = nullptr;
+  T.st_off = S.offsets.p; T.st_nbr = S.nbr.p; T.st_loc = S.st_loc.p; T.diagpos = S.diagpos.p;
+  T.tile_voff = S.tile_voff.p; T.tile_verts = S.tile_verts.p;
+  // row r lands at scratch[st_off[r] - st_off[r0]]: the kernel indexes `values` by the stencil offsets themselves, so the
+  // base handed to it lies lat_sb0 doubles below the scratch block.  Deliberate; formed as an integer so that no pointer
+  // arithmetic leaves the allocation, and only values[st_off[r0] ..] is ever touched.
+  T.indptr = S.offsets.p;
+  T.values = reinterpret_cast<double*>(reinterpret_cast<uintptr_t>(S.lat_scratch.p) - sizeof(double) * (uintptr_t)S.lat_sb0);
+  T.bc0 = nullptr; T.bc1 = nullptr; T.inline_bits = 1u; T.fresh = 1; T.error = err.p; T.ndofs = V->ndofs;
+  T.lat_len = 0; T.stream_blocks = 0; T.lat_tmpl = nullptr; T.lat_written = nullptr;
+  const dim3 gt = row_grid(1);
+  if (tdim == 3 && tcls == 0) launch("lattice_template", assemble_tiles_plain_kernel<3, true, 0>, gt, dim3(kWave), 0, T);
+  else if (tdim == 3) launch("lattice_template", assemble_tiles_plain_kernel<3, true, 1>, gt, dim3(kWave), 0, T);
+  else if (tcls == 0) launch("lattice_template", assemble_tiles_plain_kernel<2, true, 0>, gt, dim3(kWave), 0, T);
+  else launch("lattice_template", assemble_tiles_plain_kernel<2, true, 1>, gt, dim3(kWave), 0, T);
+  S.lat_tmpl = S.lat_scratch.p + S.lat_rel;
+  S.lat_tmpl_built = true;
+  publish_across_lanes();
+  return true;
+}
 
 // the series source term of the uncut entities of cell integral slot `mark` on a P1 space over a mesh of hex groups,
 // its entity list a located list as handed out: the staging by hex corner (cfx_row_plan::vec_groups).
@@ -5069,6 +5211,7 @@ void prepare_form_tables(cfx_form_s* a)
   if (!plan.usable || V->degree != 1 || V->bs != 1) return;
   if (!stn.usable) return;
   (void)space_stencil_tiles(V);
+  if (a->rank == 2) (void)lattice_template(V);
   plain_row_masks(a);
   if (a->rank == 1)
   {

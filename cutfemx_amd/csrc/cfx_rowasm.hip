@@ -2822,6 +2822,201 @@ const Stencil& space_stencil_tiles(cfx_space_s* V)
   return S;
 }
 
+// ---------------------------------------------------------------------------
+// Lattice rows (Stencil::lat_rows).  info: 0 largest incident-cell count, 1 representative row, 2 flagged rows,
+// 3 rows with the largest cell count, 4 stencil offset of the first row of the representative's tile, 5 of the
+// representative itself, 6 its stencil length.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) lattice_maxc_kernel(int64_t ndofs, const int64_t* __restrict__ d2c_off,
+                                                              unsigned long long* __restrict__ info)
+{
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int c = r < ndofs ? (int)(d2c_off[r + 1] - d2c_off[r]) : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c = max(c, __shfl_xor(c, o, 64));
+  if (threadIdx.x % kWave == 0 && (unsigned long long)c > *reinterpret_cast<volatile unsigned long long*>(&info[0]))
+    atomicMax(&info[0], (unsigned long long)c);
+}
+
+// the row ndofs / 2, moved forward (and around) to the next row with the largest cell count
+__global__ void __launch_bounds__(kBlock) lattice_pick_kernel(int64_t ndofs, const int64_t* __restrict__ d2c_off,
+                                                              const int64_t* __restrict__ st_off,
+                                                              unsigned long long* __restrict__ info)
+{
+  __shared__ int s_hit;
+  const int64_t maxc = (int64_t)info[0];
+  const int64_t start = ndofs / 2;
+  for (int64_t base = 0; base < ndofs; base += kBlock)
+  {
+    if (threadIdx.x == 0) s_hit = kBlock;
+    __syncthreads();
+    const int64_t k = base + threadIdx.x;
+    const int64_t r = k < ndofs ? (start + k) % ndofs : -1;
+    if (r >= 0 && d2c_off[r + 1] - d2c_off[r] == maxc) atomicMin(&s_hit, (int)threadIdx.x);
+    __syncthreads();
+    const int hit = s_hit;
+    if (hit < kBlock)
+    {
+      if ((int)threadIdx.x == hit)
+      {
+        const int64_t r0 = r / kRowTile * kRowTile;
+        info[1] = (unsigned long long)r;
+        info[4] = (unsigned long long)st_off[r0];
+        info[5] = (unsigned long long)st_off[r];
+        info[6] = (unsigned long long)(st_off[r + 1] - st_off[r]);
+      }
+      return;
+    }
+    __syncthreads();
+  }
+}
+
+// flag of row r: its cells carry the slot words of the representative's, and every vertex of its stencil lies at the
+// bitwise same difference from it.  (The other vertices of an incident cell sit at the stencil positions its slot word
+// names, so equal words and equal differences at every position are equal differences cell by cell.)
+__global__ void __launch_bounds__(kBlock) lattice_flag_kernel(int64_t ndofs, const int64_t* __restrict__ d2c_off,
+                                                              const uint32_t* __restrict__ slot4,
+                                                              const int64_t* __restrict__ st_off, const int32_t* __restrict__ nbr,
+                                                              const double* __restrict__ x, uint8_t* __restrict__ diagpos,
+                                                              unsigned long long* __restrict__ info)
+{
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t maxc = (int64_t)info[0], rs = (int64_t)info[1];
+  bool ok = false, top = false;
+  if (r < ndofs)
+  {
+    const int64_t cb = d2c_off[r], cs = d2c_off[rs];
+    const int nc = (int)(d2c_off[r + 1] - cb), ncs = (int)(d2c_off[rs + 1] - cs);
+    const int64_t sb = st_off[r], ss = st_off[rs];
+    const int len = (int)(st_off[r + 1] - sb), lens = (int)(st_off[rs + 1] - ss);
+    const unsigned d = diagpos[r];
+    top = nc == maxc;
+    ok = nc == ncs && len == lens && (d & kDiagPosMask) == (diagpos[rs] & kDiagPosMask);
+    for (int t = 0; ok && t < nc; ++t) ok = slot4[cb + t] == slot4[cs + t];
+    for (int k = 0; ok && k < len; ++k)
+    {
+      const int64_t v = nbr[sb + k], vs = nbr[ss + k];
+      for (int c = 0; c < 3; ++c)
+        ok = ok && __double_as_longlong(x[3 * v + c] - x[3 * r + c]) == __double_as_longlong(x[3 * vs + c] - x[3 * rs + c]);
+    }
+    diagpos[r] = (uint8_t)((d & kDiagPosMask) | (ok ? kLatFlag : 0u));
+  }
+  const int n_ok = __popcll(__ballot(ok)), n_top = __popcll(__ballot(top));
+  if (threadIdx.x % kWave == 0)
+  {
+    if (n_ok) atomicAdd(&info[2], (unsigned long long)n_ok);
+    if (n_top) atomicAdd(&info[3], (unsigned long long)n_top);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) lattice_clear_kernel(int64_t ndofs, uint8_t* __restrict__ diagpos)
+{
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r < ndofs) diagpos[r] &= (uint8_t)kDiagPosMask;
+}
+
+bool lattice_rows_on()
+{
+  const char* env = getenv("CFX_LATTICE_ROWS");
+  return !(env && env[0] == '0');
+}
+
+const Stencil& space_lattice(cfx_space_s* V)
+{
+  Stencil& S = const_cast<Stencil&>(space_stencil_tiles(V));
+  if (S.lat_built || !S.tiles_usable) return S;
+  if (!lattice_rows_on() || V->ndofs < 1 || V->mesh->x.n < 3 * V->ndofs) { S.lat_built = true; return S; }
+  const Adjacency& adj = V->dof_cells();
+  DevArray<unsigned long long> info(8);
+  info.zero();
+  const dim3 grid = grid_for(V->ndofs, kBlock);
+  launch("lattice_rows", lattice_maxc_kernel, grid, dim3(kBlock), 0, V->ndofs, adj.offsets.p, info.p);
+  launch("lattice_rows", lattice_pick_kernel, dim3(1), dim3(kBlock), 0, V->ndofs, adj.offsets.p, S.offsets.p, info.p);
+  launch("lattice_rows", lattice_flag_kernel, grid, dim3(kBlock), 0, V->ndofs, adj.offsets.p, S.slot4.p, S.offsets.p,
+         S.nbr.p, V->mesh->x.p, S.diagpos.p, info.p);
+  // One read-back of mesh-static numbers: it does not depend on the counts of a speculative step, so it is not put
+  // under the step's void guard, and lat_built is set after it -- a throw leaves the flags to be written again.
+  unsigned long long h[8];
+  {
+    unsigned long long* pin = static_cast<unsigned long long*>(pinned_scratch());
+    CFX_HIP(hipMemcpyAsync(pin, info.p, sizeof(h), hipMemcpyDeviceToHost, ctx().stream));
+    CFX_HIP(hipStreamSynchronize(ctx().stream));
+    for (int k = 0; k < 8; ++k) h[k] = pin[k];
+    ++sync_counter();
+  }
+  const int64_t flagged = (int64_t)h[2], top = (int64_t)h[3];
+  // worth a code path only where it serves most of the complete rows (else: no flag, no template)
+  if (2 * flagged < top || flagged == 0 || h[6] == 0 || h[6] > 63)
+  {
+    launch("lattice_rows", lattice_clear_kernel, grid, dim3(kBlock), 0, V->ndofs, S.diagpos.p);
+    S.lat_rows = 0;
+  }
+  else
+  {
+    S.lat_written.alloc(1);
+    S.lat_written.zero();
+    S.lat_rstar = (int64_t)h[1];
+    S.lat_sb0 = (int64_t)h[4];
+    S.lat_rel = (int)((int64_t)h[5] - (int64_t)h[4]);
+    S.lat_len = (int)h[6];
+    S.lat_rows = flagged;
+  }
+  S.lat_built = true;
+  publish_across_lanes();
+  return S;
+}
+
+// first plain row of its tile that does not take the lattice template (see assemble_tiles_plain_kernel: the same test)
+struct LatTileStart
+{
+  const int32_t* rows;
+  const unsigned long long* masks;
+  const uint8_t* uniform;
+  const uint8_t* diagpos;
+  unsigned long long full;
+  unsigned bits;
+  __device__ bool templ(int64_t i) const
+  {
+    return lattice_template_row(diagpos[rows[i]], uniform[i], masks[i], bits, full);
+  }
+  __device__ bool operator()(int64_t i) const
+  {
+    if (templ(i)) return false;
+    const int32_t t = rows[i] / kRowTile;
+    for (int64_t j = i - 1; j >= 0 && rows[j] / kRowTile == t; --j)
+      if (!templ(j)) return false;
+    return true;
+  }
+};
+
+bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits)
+{
+  cfx_row_plan& plan = row_plan(a);
+  if (plan.lat_tiles_built) return plan.lat_bits == inline_bits && plan.lat_bits != 0;
+  const Stencil& S = space_lattice(a->V);
+  if (S.lat_rows <= 0 || !plan.plain_masks_built || plan.plain_masks.n == 0 || plan.n_plain_tiles.cap() == 0) return false;
+  // (the list's own flag is set last: a throw out of the compaction leaves it to be built again, never a plan that
+  // answers true with an empty list, whose non-template plain rows nobody would write)
+  DevArray<int32_t> first;
+  TileIdEmit emit{plan.plain_rows.p, nullptr};
+  bool emitted = false;
+  auto pre = [&](int64_t cap) { plan.lat_tile_id.alloc(cap); emit.ids = plan.lat_tile_id.p; emitted = true; };
+  const LatTileStart pred{plan.plain_rows.p, plan.plain_masks.p, plan.plain_uniform.p, S.diagpos.p,
+                          (1ull << S.lat_len) - 1ull, inline_bits};
+  plan.n_lat_tiles = compact_count("plan_plain_tiles", "plan.lattice_tiles", plan.n_plain_rows.devn(), pred, first, &emit, pre);
+  plan.lat_tile_first = std::move(first);
+  if (!emitted && plan.n_lat_tiles.cap() > 0)
+  {
+    plan.lat_tile_id.alloc(plan.n_lat_tiles.cap());
+    launch("plan_plain_tiles", tile_ids_kernel, grid_for(plan.n_lat_tiles.cap()), dim3(kBlock), 0, plan.n_lat_tiles,
+           plan.lat_tile_first.p, plan.plain_rows.p, plan.lat_tile_id.p);
+  }
+  plan.lat_bits = inline_bits;
+  plan.lat_tiles_built = true;
+  publish_across_lanes();
+  return inline_bits != 0;
+}
+
 bool space_dof_verts(cfx_space_s* V)
 {
   if (V->dof_verts_built) return V->dof_verts_ok;
@@ -2882,6 +3077,40 @@ bool plain_row_masks(cfx_form_s* a, int32_t* counts, int* maxlen)
     TileIdEmit emit{plan.plain_rows.p, nullptr};
     bool emitted = false;
     auto pre = [&](int64_t cap) { plan.plain_tile_id.alloc(cap); emit.ids = plan.plain_tile_id.p; emitted = true; };
+    // a bilinear form on a space with lattice rows: the tiles the tile kernel still has work in (those with a plain row
+    // that does not take the template) come out of the same passes.  Which integrals are inline stiffness is decided
+    // at assembly (RowIntegral::std_inline); the list is built for the likely answer and used only if it was right.
+    unsigned lat_bits = 0;
+    if (a->rank == 2 && lattice_rows_on())
+    {
+      for (int sl = 0; sl < plan.n_cell_slots && sl < 4; ++sl)
+      {
+        const cfx_integral_dev& I = a->integrals[plan.cell_slot_integral[sl]];
+        if (I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0 && I.coefficients.empty()) lat_bits |= 1u << sl;
+      }
+    }
+    const Stencil* lat = lat_bits ? &space_lattice(V) : nullptr;
+    if (lat && lat->lat_rows > 0)
+    {
+      DevArray<int32_t> lfirst;
+      TileIdEmit lemit{plan.plain_rows.p, nullptr};
+      const LatTileStart lpred{plan.plain_rows.p, plan.plain_masks.p, plan.plain_uniform.p, lat->diagpos.p,
+                               (1ull << lat->lat_len) - 1ull, lat_bits};
+      const char* const sites[2] = {"plan.plain_tiles", "plan.lattice_tiles"};
+      Count totals[2];
+      compact_count_pair("plan_plain_tiles", sites, plan.n_plain_rows.devn(), TileStart{plan.plain_rows.p}, lpred, emit, lemit,
+                         first, lfirst, totals, [&](int64_t ca, int64_t cb)
+                         {
+                           plan.plain_tile_id.alloc(ca); emit.ids = plan.plain_tile_id.p;
+                           plan.lat_tile_id.alloc(cb); lemit.ids = plan.lat_tile_id.p;
+                         });
+      plan.n_plain_tiles = totals[0]; plan.n_lat_tiles = totals[1];
+      plan.plain_tile_first = std::move(first);
+      plan.lat_tile_first = std::move(lfirst);
+      plan.lat_tiles_built = true; plan.lat_bits = lat_bits;
+      publish_across_lanes();
+      return counts != nullptr;
+    }
     plan.n_plain_tiles = compact_count("plan_plain_tiles", "plan.plain_tiles", plan.n_plain_rows.devn(),
                                        TileStart{plan.plain_rows.p}, first, &emit, pre);
     plan.plain_tile_first = std::move(first);

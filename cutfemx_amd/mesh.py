@@ -203,6 +203,21 @@ class FunctionSpace:
         # (cell_neighbours: the cell -> cell table + the vertex runs of the culled classification, both the mesh's)
         return dict(dof_cells=int(b[0]), row_stencil=int(b[1]), row_tiles=int(b[2]), cell_neighbours=int(b[3]))
 
+    def _lattice(self):
+        n, w = C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.lib().cfx_space_lattice_rows(self._h, C.byref(n), C.byref(w)))
+        return int(n.value), int(w.value)
+
+    def lattice_rows(self) -> int:
+        """Rows whose cells are bitwise translates of one representative row's (cfx_space_lattice_rows): uncut
+        stiffness rows among them are copied from one stored row.  0: no such table for this space."""
+        return self._lattice()[0]
+
+    def lattice_template_rows(self) -> int:
+        """Rows written from the stored row since the space was created; the difference across an assembly is that
+        assembly's count."""
+        return self._lattice()[1]
+
     @property
     def dofmap(self) -> np.ndarray:
         if hasattr(self, "_host_dofmap"):

@@ -393,6 +393,15 @@ int cfx_space_create(cfx_mesh_t mesh, int degree, int bs, int64_t ndofs,
  * unions, st_loc) and the cell blocks a linear form is summed over (slots, segments, dof -> partials lists), [3] the
  * mesh's cell -> cell table (built by the first ghost-penalty query). */
 int cfx_space_static_bytes(cfx_space_t V, int64_t bytes[4]);
+/* Lattice rows of a P1 space on the geometry dofmap: *n = the rows whose incident cells are bitwise translates of the
+ * cells of one representative row (equal local layout, equal fl(x_o - x_r) compared as 64-bit integers), 0 when the
+ * space has no such table, when fewer than half of the complete rows qualify, or under CFX_LATTICE_ROWS=0.  Where all
+ * cells around such a row are uncut entities of one inline stiffness integral and no boundary marks apply, the assembly
+ * copies the row from one stored row instead of running the element loop of
+ * cpp/dolfinx_custom_data/fem/assemble_matrix_impl.h:103-188 over its cells; the copy is bit for bit what the
+ * deterministic kernel computes.  *template_rows (may be NULL) = rows written that way since the space was created:
+ * the difference across one cfx_assemble_matrix call is that call's count. */
+int cfx_space_lattice_rows(cfx_space_t V, int64_t* n, int64_t* template_rows);
 int cfx_space_destroy(cfx_space_t V);
 
 /* ---- forms: dolfinx_custom_data::fem::Form, Form.h:119-178, built as in
