@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/cutfemx_amd.h"
+#include "cfx_switches.h"
 
 namespace cfx
 {
@@ -127,8 +128,8 @@ inline void launch(const char* name, K kernel, dim3 grid, dim3 block, size_t shm
   Context& c = ctx();
   if (grid.x == 0) return;
   c.last_launch = name;
-  static const bool trace = getenv("CFX_LAUNCH_TRACE") != nullptr; // the launch sequence of a step on stderr
-  if (trace) fprintf(stderr, "cutfemx_amd: launch %s grid %u\n", name, grid.x);
+  if (env_present_once<Sw::LAUNCH_TRACE>()) // the launch sequence of a step on stderr
+    fprintf(stderr, "cutfemx_amd: launch %s grid %u\n", name, grid.x);
   // HIP launches at most 2^32 - 1 work-items per dimension; a larger grid is cut short silently
   if ((uint64_t)grid.x * block.x > 0xffffffffull)
     throw Error(CFX_ERR_RUNTIME, std::string(name) + ": launch exceeds 2^32 threads");
@@ -145,8 +146,8 @@ inline void launch(const char* name, K kernel, dim3 grid, dim3 block, size_t shm
     hipLaunchKernelGGL(kernel, grid, block, shmem, c.stream, args...);
   }
   CFX_HIP(hipGetLastError());
-  static const bool sync_each = getenv("CFX_LAUNCH_SYNC") != nullptr; // diagnostics: a fault surfaces at its own launch
-  if (sync_each) CFX_HIP(hipStreamSynchronize(c.stream));
+  if (env_present_once<Sw::LAUNCH_SYNC>()) // diagnostics: a fault surfaces at its own launch
+    CFX_HIP(hipStreamSynchronize(c.stream));
 }
 
 // grid of one-wavefront blocks whose kernel loops `for (blk = blockIdx.x; ...; blk += gridDim.x)`
@@ -964,7 +965,6 @@ struct cfx_row_plan
   cfx::DevArray<int32_t> facet_rows;  // [nfacets*4]
   cfx::DevArray<uint8_t> facet_slot;  // facet integral slot of each row
   cfx::DevArray<int64_t> d2f_offsets; // dof -> facets incidence
-  bool d2f_sorted = false; // built by the sort path: every list already in ascending facet order
   cfx::DevArray<int32_t> d2f;
   int n_cell_slots = 0, n_facet_slots = 0;
   // per cell slot: bitset of its uncut entities + exclusive popcount ranks (entity index lookup)

@@ -2409,9 +2409,8 @@ void classify(cfx_cut_t cut)
     const uint8_t* phi = codes.p;
     {
       // implicit-structured variant (opt-in): generated box mesh, P1 level set on the geometry dofmap
-      const char* ib = getenv("CFX_IMPLICIT_BOX");
       cfx_mesh_t mesh = cut->mesh;
-      if (ib && ib[0] == '1' && cut->host_width == 0 && mesh->box_n > 0 && cut->ls_dofmap.p == mesh->conn.p
+      if (env_is<Sw::IMPLICIT_BOX>('1') && cut->host_width == 0 && mesh->box_n > 0 && cut->ls_dofmap.p == mesh->conn.p
           && cut->ls_ndofs_cell == mesh->tdim + 1)
       {
         const int64_t ncubes = nc / (mesh->tdim == 3 ? 6 : 2);
@@ -2445,9 +2444,8 @@ void classify(cfx_cut_t cut)
       // block culling (classify_culled_kernel): cells as hosts, level set on the geometry dofmap (the summary is the
       // mesh's), P1; CFX_CLASSIFY_CULL=0: cell by cell
       cfx_mesh_t mesh = cut->mesh;
-      const char* cc = getenv("CFX_CLASSIFY_CULL");
       const int nd = cut->ls_ndofs_cell;
-      if (!(cc && cc[0] == '0') && cut->host_width == 0 && cut->ls_dofmap.p == mesh->conn.p && nd == mesh->tdim + 1
+      if (env_on<Sw::CLASSIFY_CULL>() && cut->host_width == 0 && cut->ls_dofmap.p == mesh->conn.p && nd == mesh->tdim + 1
           && nc == mesh->ncells && (nd == 3 || nd == 4))
       {
         const int64_t nb = (nc + kClassBlock - 1) / kClassBlock;

@@ -132,7 +132,7 @@ ChainState chain_state(int64_t ntiles);
 // workgroups walking their tiles one after the other).
 inline ChainState fused_chain(bool publish, int64_t ntiles)
 {
-  static const int64_t max_tiles = []() { const char* e = getenv("CFX_FUSED_TILES"); return e ? atoll(e) : (int64_t)512; }();
+  const int64_t max_tiles = env_int_once<Sw::FUSED_TILES>(512);
   return publish && ntiles <= max_tiles ? chain_state(ntiles) : ChainState{};
 }
 

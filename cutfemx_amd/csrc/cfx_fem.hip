@@ -966,9 +966,8 @@ void launch_integral_t(const cfx_form_s* a, const cfx_integral_dev& I, AsmArgs A
     return;
   }
   // staged element tensors of the elasticity term on 3-D vector spaces: the MFMA kernel (CFX_MFMA=0: generic rows)
-  const char* mf = getenv("CFX_MFMA");
   const bool mfma_tensors = TDIM == 3 && BS == 3 && a->rank == 2 && A.dump != nullptr && !single && !A.lift_markers
-                            && A.kernel == CFX_K_ELASTICITY && !A.coeff && !(mf && mf[0] == '0');
+                            && A.kernel == CFX_K_ELASTICITY && !A.coeff && env_on<Sw::MFMA>();
   // a resident grid of wavefronts, each walking its share of the cells
   auto mfma_grid = [](int64_t n) { return dim3((unsigned)std::min<int64_t>(n, 256 * 32)); };
   if ((parts & 1) && (!single || !use_rule))
@@ -1001,8 +1000,7 @@ void launch_integral_t(const cfx_form_s* a, const cfx_integral_dev& I, AsmArgs A
     A.point_data = I.point_data.n > 0 ? I.point_data.p : nullptr;
     if (A.n.cap > 0)
     {
-      const char* spec = getenv("CFX_CUT_TENSORS_P1");
-      if (a->rank == 2 && DEG == 1 && BS == 1 && A.dump && !single && !A.coeff && !(spec && spec[0] == '0')
+      if (a->rank == 2 && DEG == 1 && BS == 1 && A.dump && !single && !A.coeff && env_on<Sw::CUT_TENSORS_P1>()
           && (A.kernel == CFX_K_STIFFNESS || A.kernel == CFX_K_MASS || A.kernel == CFX_K_NITSCHE))
       {
         if constexpr (DEG == 1 && BS == 1)
@@ -1300,8 +1298,7 @@ __global__ void mark_dofs_kernel(int64_t ncells_active, const int32_t* __restric
 // CFX_ASSEMBLY=atomic selects the entity-parallel FP64-atomic kernels (tests cover both paths)
 bool force_atomic()
 {
-  const char* e = getenv("CFX_ASSEMBLY");
-  return e && strcmp(e, "atomic") == 0;
+  return env_equals<Sw::ASSEMBLY>("atomic");
 }
 
 struct FlagSet

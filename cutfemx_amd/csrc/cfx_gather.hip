@@ -2681,12 +2681,10 @@ __global__ void __launch_bounds__(kWave, CFX_TILE_WAVES) assemble_tiles_plain_ke
 // 7 KB), the rows of cut cells come from the stage-1 rule tensors.  No facet items: forms with
 // facet integrals on block spaces keep the entity-parallel path.
 // ---------------------------------------------------------------------------
-// INLINE = false (default): uncut tensors are staged, the elasticity arithmetic is not compiled in
-// and the kernel fits 4 waves/SIMD.
-// INLINE: how the uncut items get their row -- 0 staged tensors, 1 quadrature row (cell_local_row), 2 closed-form
-// degree-2 elasticity row (p2_elasticity_row: std_inline == 3)
+// INLINE: how the uncut items get their row -- 0 (default) staged tensors: the elasticity arithmetic is not compiled in
+// and the kernel fits 4 waves/SIMD; 2 closed-form degree-2 elasticity row (p2_elasticity_row: std_inline == 3)
 template <int TDIM, int DEG, int BS, int G, int CAP, bool ORDERED, int INLINE>
-__global__ void __launch_bounds__(kWave, INLINE == 1 ? 2 : CFX_BLOCK_WAVES) assemble_rows_block_kernel(RowArgs A)
+__global__ void __launch_bounds__(kWave, CFX_BLOCK_WAVES) assemble_rows_block_kernel(RowArgs A)
 {
   constexpr int ND = Elem<TDIM, DEG>::ND;
   constexpr int NLOC = ND * BS;
@@ -2773,17 +2771,6 @@ __global__ void __launch_bounds__(kWave, INLINE == 1 ? 2 : CFX_BLOCK_WAVES) asse
               jacobian<TDIM>(g);
               const double E = I.params[0], nu = I.params[1];
               p2_elasticity_row<TDIM>(g, lr, kc, E * nu / ((1.0 + nu) * (1.0 - 2.0 * nu)), E / (2.0 * (1.0 + nu)), acc);
-            }
-            else if constexpr (INLINE == 1)
-            {
-              Geo<TDIM> g;
-              load_cell<TDIM>(A.x, A.conn, c, g);
-              jacobian<TDIM>(g);
-              int npts;
-              const double* wts;
-              const double* pts = ref_rule(TDIM, I.qdegree, npts, wts);
-              cell_local_row<TDIM, DEG, BS, 2>(I.kernel, I.params, I.point_stride, g, 0.0, npts, pts, wts, fabs(g.detJ),
-                                               nullptr, lr, kc, acc);
             }
           }
           else
@@ -3113,8 +3100,7 @@ __global__ void __launch_bounds__(kWave) assemble_vec_rows_kernel(RowArgs A)
 
 bool deterministic()
 {
-  const char* e = getenv("CFX_DETERMINISTIC");
-  return e && e[0] == '1';
+  return env_is<Sw::DETERMINISTIC>('1');
 }
 
 // stage 2, bilinear forms, degree 2: the rows that copied their static neighbour list (cfx_pattern_s::full_rows --
@@ -3621,9 +3607,8 @@ __global__ void __launch_bounds__(kWave, CFX_BLOCK_P2_WAVES) assemble_rows_block
 inline bool p2_elasticity_closed(const cfx_form_s* a, const cfx_integral_dev& I)
 {
   const cfx_space_s* V = a->V;
-  const char* cf = getenv("CFX_P2_CLOSED");
   return a->rank == 2 && V->degree == 2 && V->bs == V->mesh->tdim && I.type == CFX_CELL && I.kernel == CFX_K_ELASTICITY
-         && I.coefficient.n == 0 && I.qdegree >= 2 && !(cf && cf[0] == '0');
+         && I.coefficient.n == 0 && I.qdegree >= 2 && env_on<Sw::P2_CLOSED>();
 }
 
 // ---------------------------------------------------------------------------
@@ -3842,9 +3827,8 @@ template <int DEG>
 inline bool source_series_ok(const cfx_space_s* V, const cfx_integral_dev& I)
 {
   const int field = (int)I.params[0];
-  const char* fs = getenv("CFX_SOURCE_SERIES");
   return DEG == 1 && I.kernel == CFX_L_SOURCE && I.coefficient.n == 0 && (field == CFX_F_SINPROD || field == CFX_F_POISSON_RHS)
-         && V->dofmap.p == V->mesh->conn.p && !(fs && fs[0] == '0');
+         && V->dofmap.p == V->mesh->conn.p && env_on<Sw::SOURCE_SERIES>();
 }
 
 // stage 1 of a linear form by cell block: the partials of the uncut cells of integral I (mark bit `mark`)
@@ -3952,8 +3936,7 @@ void vec_tensors(cfx_form_s* L, const cfx_integral_dev& I, bool runtime, double*
 // the rule integrals of a degree-2 scalar bilinear form that cut_tensors_p2_kernel can sum into one tensor per cut cell
 inline bool p2_cut_tensors_ok(const cfx_form_s* a)
 {
-  const char* e = getenv("CFX_P2_CUT_TENSORS");
-  if (e && e[0] == '0') return false;
+  if (!env_on<Sw::P2_CUT_TENSORS>()) return false;
   if (a->rank != 2 || a->V->degree != 2 || a->V->bs != 1) return false;
   bool any = false;
   for (const auto& I : a->integrals)
@@ -3996,21 +3979,19 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
       R.std_rank = plan.std_rank[s].p;
     }
     // uncut P1 stiffness is one point: cheaper to recompute than to stage
-    const char* inl = getenv("CFX_STD_INLINE");
     // (degree 2: staging 100 doubles per uncut cell would be 38 GB at config 4 -- the row of the
     // local tensor is recomputed per (row, cell) item instead, 4-14 quadrature points)
     const bool inline_ok = BS > 1 ? (I.kernel == CFX_K_ELASTICITY || I.kernel == CFX_K_MASS || I.kernel == CFX_K_STIFFNESS)
                                   : (DEG == 1 ? I.kernel == CFX_K_STIFFNESS
                                               : (I.kernel == CFX_K_STIFFNESS || I.kernel == CFX_K_MASS));
-    R.std_inline = (a->rank == 2 && inline_ok && kRowsInline<DEG> && I.coefficient.n == 0 && !(inl && inl[0] == '0')) ? 1 : 0;
-    if (BS > 1 && !(inl && inl[0] == '1')) R.std_inline = 0; // block spaces stage their uncut tensors (see assemble_matrix_rows)
-    if (R.std_inline && A.iso_geometry && !(inl && inl[0] == '1')) R.std_inline = 2;
+    R.std_inline = (a->rank == 2 && inline_ok && kRowsInline<DEG> && I.coefficient.n == 0) ? 1 : 0;
+    if (BS > 1) R.std_inline = 0; // block spaces stage their uncut tensors (see assemble_matrix_rows)
+    if (R.std_inline && A.iso_geometry) R.std_inline = 2;
     if (R.std_inline == 1) A.iso_geometry = 0; // a generic inline integral: the ISO kernel cannot serve this form
     {
       // degree-2 scalar stiffness without coefficient: closed-form row per item, no staged tensors
-      const char* cf = getenv("CFX_P2_CLOSED");
       if (DEG == 2 && BS == 1 && a->rank == 2 && I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0 && I.qdegree >= 2
-          && !(cf && cf[0] == '0'))
+          && env_on<Sw::P2_CLOSED>())
         R.std_inline = 3;
       // ... and the vector-valued elasticity term likewise (closed-form block rows)
       if (DEG == 2 && BS == TDIM && p2_elasticity_closed(a, I)) R.std_inline = 3;
@@ -4021,8 +4002,7 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
     {
       // linear forms whose entity list covers a good part of the mesh stage [ND][ncells]: the rows index the record by
       // the cell they hold anyway, without the bitset + rank lookup of the entity index (two gathers per item)
-      const char* bc = getenv("CFX_VEC_BY_CELL");
-      const bool by_cell = a->rank == 1 && BS == 1 && !st.vec_t2 && n_ent * 4 >= V->mesh->ncells && !(bc && bc[0] == '0');
+      const bool by_cell = a->rank == 1 && BS == 1 && !st.vec_t2 && n_ent * 4 >= V->mesh->ncells;
       st.buffers.emplace_back((by_cell ? V->mesh->ncells : n_ent) * tsize);
       R.std_tensors = st.buffers.back().p;
       R.n_std = by_cell ? V->mesh->ncells : n_ent;
@@ -4041,9 +4021,8 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
     {
       R.parent_map = I.rules->parent_map.p; R.nr = rule_bound(I.rules);
       R.rule_keys = plan.rule_keys[s].p; R.rule_first = plan.rule_first[s].p; R.rule_mask = plan.rule_mask[s];
-      const char* cm = getenv("CFX_P2_MOMENTS");
       const bool moments = DEG == 2 && BS == 1 && a->rank == 2 && I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0
-                           && !(cm && cm[0] == '0');
+                           && env_on<Sw::P2_MOMENTS>();
       st.buffers.emplace_back(n_rules * (moments ? 16 : tsize));
       R.rule_tensors = st.buffers.back().p;
       R.rule_moments = moments ? 1 : 0;
@@ -4098,14 +4077,15 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
     A.special_mark = plan.special_mark.p; A.special_pos = plan.special_pos.p;
     // 3-D P1 scalar spaces: stage 1 stores the macro tensor already folded over the shared dofs, 25 doubles per
     // facet instead of 64 (fold_facets = 2); elsewhere the P1 fold happens in the gather (1) or not at all (0)
-    const char* fe = getenv("CFX_FACET_FOLD_STAGE1");
+    const char fe = env_char<Sw::FACET_FOLD_STAGE1>();
+    const bool fold1 = fe != '0', fold1_records = fold1 && fe != '2';
     bool user_facets = false; // (integrands compiled at run time stage the whole macro tensor: folded in the gather, or not)
     for (int s = 0; s < plan.n_facet_slots; ++s)
       user_facets = user_facets || user_integrand_known(a->integrals[plan.facet_slot_integral[s]].kernel);
-    if (TDIM == 3 && DEG == 1 && BS == 1 && A.fold_facets && a->rank == 2 && !(fe && fe[0] == '0') && !user_facets) A.fold_facets = 2;
+    if (TDIM == 3 && DEG == 1 && BS == 1 && A.fold_facets && a->rank == 2 && fold1 && !user_facets) A.fold_facets = 2;
     // ... and when every facet term is the gradient jump over standard facets, the folded tensor is rank one:
     // stage 1 stores its vector and weight (8 doubles per facet, fold_facets = 3)
-    bool rank_one = DEG == 1 && BS == 1 && A.fold_facets && a->rank == 2 && !(fe && (fe[0] == '0' || fe[0] == '2'));
+    bool rank_one = DEG == 1 && BS == 1 && A.fold_facets && a->rank == 2 && fold1_records;
     for (int s = 0; s < plan.n_facet_slots; ++s)
     {
       const cfx_integral_dev& I = a->integrals[plan.facet_slot_integral[s]];
@@ -4113,7 +4093,7 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
     }
     if (rank_one) A.fold_facets = 3;
     // degree 2, scalar: nq rank-one records per facet when every facet term is the gradient jump at one degree
-    if (DEG == 2 && A.fold_facets && a->rank == 2 && !(fe && fe[0] == '0'))
+    if (DEG == 2 && A.fold_facets && a->rank == 2 && fold1)
     {
       bool low = true;
       int qd = -1;
@@ -4164,10 +4144,9 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
   if constexpr (DEG == 2)
   {
     cfx_row_plan& plan0 = row_plan(a);
-    const char* fs0 = getenv("CFX_ROWS_SPLIT");
     const int mr0 = P->max_row_len;
     combine_cuts = P->split_plan == plan0.serial && mr0 > 64 && mr0 <= 256
-                   && (plan0.n_special_rows.value() * 2 <= plan0.n_active_rows.value() || (fs0 && fs0[0] == '1'))
+                   && (plan0.n_special_rows.value() * 2 <= plan0.n_active_rows.value() || env_is<Sw::ROWS_SPLIT>('1'))
                    && plan0.n_special_rows.value() > 0
                    && p2_cut_tensors_ok(a);
   }
@@ -4179,7 +4158,7 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
   // `fresh` = MatrixCSR.set_value(0) fused into this call (nothing has written to `values` yet: stage 1 fills its own
   // buffers).  P1 on the split path: every active row has a FIRST writer that stores (the tile / plain kernels their
   // rows, assemble_rows_p1 the rows it is given), so only the inactive rows (one diagonal entry each) are zeroed --
-  // 0.2 instead of 0.7 ms at 512^3; every other path fills the whole array first.  CFX_LAZY_ZERO=0: always fill.
+  // 0.2 instead of 0.7 ms at 512^3; every other path fills the whole array first.
   bool lazy_zero = false;
   auto fill_all = [&]() { if (fresh) dev_fill(values, 0, sizeof(double) * (size_t)P->nnz.cap()); };
   if constexpr (DEG > 1)
@@ -4215,12 +4194,10 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
         if (A.cell[s].std_inline == 2) inline_bits |= 1u << s;
         else if (A.cell[s].std_bits) all_inline = false; // staged uncut tensors: generic path
       }
-      const char* fs1 = getenv("CFX_ROWS_SPLIT");
-      const bool split_p1 = all_inline && inline_bits && (2 * plan.n_special_rows.hint() <= plan.n_active_rows.hint() || (fs1 && fs1[0] == '1'));
-      const char* lz = getenv("CFX_LAZY_ZERO");
+      const bool split_p1 = all_inline && inline_bits && (2 * plan.n_special_rows.hint() <= plan.n_active_rows.hint() || env_is<Sw::ROWS_SPLIT>('1'));
       // (only when P was laid out from this very plan: a pattern of a larger form -- several forms assembled into one
       // matrix -- has full-length rows where this plan has none, and they must all be zeroed)
-      lazy_zero = fresh && split_p1 && P->built_plan == plan.serial && !(lz && lz[0] == '0');
+      lazy_zero = fresh && split_p1 && P->built_plan == plan.serial;
       if (!lazy_zero) fill_all();
       if (split_p1)
       {
@@ -4287,8 +4264,7 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
             }
           }
           const dim3 gq = row_grid((Q.n_active.cap + (kWave / CFX_PLAIN_G) - 1) / (kWave / CFX_PLAIN_G));
-          const char* stage_env = getenv("CFX_PLAIN_STAGE");
-          const bool stage = stn.max_len <= 32 && !(stage_env && stage_env[0] == '0');
+          const bool stage = stn.max_len <= 32 && env_on<Sw::PLAIN_STAGE>();
           // plain rows are subsets of their stencil: the LDS footprint follows the longest stencil
           // (16 covers the 15-vertex stencil of Kuhn meshes: 4.4 KB per block instead of 8.4 KB)
           const int plain_cap = stn.max_len <= 16 ? 16 : (stn.max_len <= 32 ? 32 : 64);
@@ -4340,8 +4316,7 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
       // cells come as combined tensors and the pattern kept the other hashed rows apart: then every active row has
       // exactly one writer and only the inactive rows are zeroed
       const bool one_pass = combine_cuts && A.cut_tensors != nullptr && P->odd_plan == plan.serial && P->full_plan == plan.serial;
-      const char* lz = getenv("CFX_LAZY_ZERO");
-      lazy_zero = fresh && one_pass && P->built_plan == plan.serial && !(lz && lz[0] == '0');
+      lazy_zero = fresh && one_pass && P->built_plan == plan.serial;
       if (!lazy_zero) fill_all();
       else
         launch("zero_inactive_rows", zero_inactive_rows_kernel, grid_for(P->nrows), dim3(kBlock), 0, P->nrows, 1, plan.rowmark.p,
@@ -4349,9 +4324,8 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
       // degree 2: (a) the uncut items of every row with the lean kernel, short rows (<= 64 columns:
       // the edge dofs, ~5 cells each) 8 lanes per row, long rows 16; (b) rule + facet items of the
       // interface rows with the full kernel.  Needs the row partition made with the pattern.
-      const char* fs = getenv("CFX_ROWS_SPLIT"); // '1': split whatever the share of the interface rows (tests on small meshes)
       if (P->split_plan == plan.serial && mr > 64 && mr <= 256
-          && (plan.n_special_rows.value() * 2 <= plan.n_active_rows.value() || (fs && fs[0] == '1')))
+          && (plan.n_special_rows.value() * 2 <= plan.n_active_rows.value() || env_is<Sw::ROWS_SPLIT>('1')))
       {
         split = true;
 #define CFX_LEAN(GG, CAPP, ROWS, NROWS)                                                                              \
@@ -4370,7 +4344,7 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
         bool lean_ok = one_pass && (plan.nfacets.value() == 0 || (A.fold_facets == 3 && A.facet_tensors != nullptr));
         for (int q = 0; q < A.n_cell; ++q)
           lean_ok = lean_ok && (A.cell[q].std_bits == nullptr || A.cell[q].std_inline == 3);
-        if (const char* li = getenv("CFX_P2_INTERFACE")) lean_ok = lean_ok && li[0] != '0';
+        lean_ok = lean_ok && env_on<Sw::P2_INTERFACE>();
 
         if (lean_ok) {}
         else if (one_pass)
@@ -4515,13 +4489,8 @@ int run_matrix_block(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const i
   {
     const bool det = deterministic();
     const int mr = P->max_row_len; // scalar columns per row
-    bool inl = false, closed = false;
-    for (int s = 0; s < A.n_cell; ++s)
-    {
-      inl = inl || (A.cell[s].std_inline != 0 && A.cell[s].std_inline != 3);
-      closed = closed || A.cell[s].std_inline == 3;
-    }
-    require(!(inl && closed), CFX_ERR_RUNTIME, "assemble_matrix: mixed inline modes on a block space");
+    bool closed = false; // (prepare leaves a block space's uncut integrals staged, 0, or closed-form, 3)
+    for (int s = 0; s < A.n_cell; ++s) closed = closed || A.cell[s].std_inline == 3;
 #define CFX_BLOCK_V(GG, CAPP, ORD, INL) \
   launch("assemble_rows_block", assemble_rows_block_kernel<TDIM, DEG, BS, GG, CAPP, ORD, INL>, grid, dim3(kWave), 0, A)
 #define CFX_BLOCK(GG, CAPP)                                                                                          \
@@ -4529,7 +4498,6 @@ int run_matrix_block(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const i
   {                                                                                                                  \
     const dim3 grid = row_grid((A.n_active.cap * BS + (kWave / GG) - 1) / (kWave / GG));                             \
     if (closed) { if (det) CFX_BLOCK_V(GG, CAPP, true, 2); else CFX_BLOCK_V(GG, CAPP, false, 2); }                   \
-    else if (inl) { if (det) CFX_BLOCK_V(GG, CAPP, true, 1); else CFX_BLOCK_V(GG, CAPP, false, 1); }                 \
     else { if (det) CFX_BLOCK_V(GG, CAPP, true, 0); else CFX_BLOCK_V(GG, CAPP, false, 0); }                          \
   } while (0)
     // degree 2: the dofs whose rows copied their static list, all BS component rows at a time
@@ -4537,12 +4505,11 @@ int run_matrix_block(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const i
     {
       cfx_row_plan& plan = row_plan(a);
       const Stencil& stn = a->V->stencil;
-      const char* bp = getenv("CFX_BLOCK_PLAIN");
       int slot = -1, n_std = 0;
       for (int s = 0; s < A.n_cell; ++s)
         if (A.cell[s].std_bits) { slot = s; ++n_std; }
       const bool full_ok = P->full_plan == plan.serial && P->n_full_rows > 0 && !bc0 && !bc1 && !det && stn.slotn_ok
-                           && stn.max_len <= 72 && n_std == 1 && !(bp && bp[0] == '0');
+                           && stn.max_len <= 72 && n_std == 1 && env_on<Sw::BLOCK_PLAIN>();
       if (full_ok && A.cell[slot].std_inline == 3)
       {
         if constexpr (BS == TDIM)
@@ -4667,15 +4634,14 @@ struct BlockChoice { bool use, merged; };
 template <int DEG>
 BlockChoice vec_block_choice(cfx_form_s* L, cfx_row_plan& plan, int slot, int count)
 {
-  const char* e = getenv("CFX_VEC_BLOCKS");
-  if ((e && e[0] == '0') || count > 1 || L->V->bs != 1 || !plan.usable) return {false, false};
+  const char e = env_char<Sw::VEC_BLOCKS>();
+  if (e == '0' || count > 1 || L->V->bs != 1 || !plan.usable) return {false, false};
   for (const auto& I : L->integrals) // (integrands compiled at run time are staged per cell, cfx_rtc.hip)
     if (user_integrand_known(I.kernel)) return {false, false};
   const bool series = count == 1 && source_series_ok<DEG>(L->V, L->integrals[plan.cell_slot_integral[slot]]);
-  if (series && !(e && e[0] == '2'))
+  if (series && e != '2')
   {
-    const char* ro = getenv("CFX_VEC_ROWORDER");
-    if (!(ro && ro[0] == '0') && plain_vec_offsets(L, (uint8_t)(1u << slot))) return {false, false};
+    if (env_on<Sw::VEC_ROWORDER>() && plain_vec_offsets(L, (uint8_t)(1u << slot))) return {false, false};
   }
   return {true, !series};
 }
@@ -4704,18 +4670,16 @@ void run_vector(cfx_form_s* L, double* b)
   if constexpr (DEG == 1)
   {
     // ... or (CFX_VEC_BLOCKS=0) its element vectors go to the plain rows directly
-    const char* ro = getenv("CFX_VEC_ROWORDER");
     bool has_user = false;
     for (const auto& I : L->integrals) has_user = has_user || user_integrand_known(I.kernel);
-    if (!st.vec_blocks && count == 1 && L->V->bs == 1 && plan.usable && !(ro && ro[0] == '0') && !has_user
+    if (!st.vec_blocks && count == 1 && L->V->bs == 1 && plan.usable && env_on<Sw::VEC_ROWORDER>() && !has_user
         && plain_vec_offsets(L, (uint8_t)(1u << slot)))
     {
       st.t2.alloc(plan.vec_groups ? 8 * plan.vec_group_cap : plan.vec_t2_total.cap());
       st.vec_t2 = st.t2.p;
       // CFX_STAGING_NAN=1 (tests): the corner planes start as NaN, so that a slot the fold adds but no hex wrote shows
       // in b whatever the block cache hands out
-      const char* sn = getenv("CFX_STAGING_NAN");
-      if (plan.vec_groups && sn && sn[0] == '1') dev_fill(st.t2.p, 0xff, sizeof(double) * (size_t)(8 * plan.vec_group_cap));
+      if (plan.vec_groups && env_is<Sw::STAGING_NAN>('1')) dev_fill(st.t2.p, 0xff, sizeof(double) * (size_t)(8 * plan.vec_group_cap));
     }
   }
   RowArgs A = prepare<TDIM, DEG>(L, st);
@@ -4848,8 +4812,7 @@ bool lattice_template(cfx_space_s* V)
 // CFX_SOURCE_GROUPS=0: never (the per-cell kernel and segments)
 bool source_groups_ok(cfx_form_s* L, uint8_t mark)
 {
-  const char* e = getenv("CFX_SOURCE_GROUPS");
-  if (e && e[0] == '0') return false;
+  if (!env_on<Sw::SOURCE_GROUPS>()) return false;
   cfx_space_s* V = L->V;
   if (!V->mesh->hex_groups || V->mesh->tdim != 3 || V->degree != 1 || V->bs != 1 || mark == 0 || (mark & 0x0Fu) != mark)
     return false;
@@ -5057,8 +5020,7 @@ __global__ void __launch_bounds__(kWave) assemble_rows2_kernel(Rect2Args A)
 
 bool assemble_rect_rows(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t* bc1, double* values, int* error)
 {
-  const char* rg = getenv("CFX_RECT_GATHER");
-  if (rg && rg[0] == '0') return false;
+  if (!env_on<Sw::RECT_GATHER>()) return false;
   cfx_space_s* V0 = a->V;
   cfx_space_s* V1 = a->V1;
   for (const auto& I : a->integrals)
@@ -5150,8 +5112,7 @@ bool assemble_matrix_rows(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, co
       for (const auto& I : a->integrals) // (closed-form uncut cells stage nothing)
         need += (size_t)((p2_elasticity_closed(a, I) ? 0 : I.n_entities.cap()) + (I.rules ? I.rules->nr.cap() : 0)) * nloc * nloc * sizeof(double);
       CFX_HIP(hipMemGetInfo(&free_b, &total_b));
-      const char* bg = getenv("CFX_BLOCK_GATHER");
-      if ((bg && bg[0] == '0') || need > free_b / 2) return false;
+      if (!env_on<Sw::BLOCK_GATHER>() || need > free_b / 2) return false;
     }
     if (V->bs != V->mesh->tdim || P->max_row_len > 256) return false;
     for (const auto& I : a->integrals) // facet items: the ghost-penalty gradient jump (extension pairs keep the entity path)

@@ -11,7 +11,6 @@
 // order, so no global atomics are issued and the sums do not depend on timing.
 #include <cstdlib>
 
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "cfx_elem.h"
 
@@ -633,8 +632,7 @@ __global__ void plan_scatter_pos_kernel(DevN n_d, const int32_t* __restrict__ ro
 // ~150 atomics.  (counts / offsets / cursors are indexed by the dof's position in the special-row list.)  A thread owns
 // one (facet, side) unit: the dof row of its cell, and for side 1 the dof row of cell 0 to drop the dofs both cells hold
 // (a shared dof lists the facet once) -- 2 nd loads per unit where one thread per pair paid 1 + nd loads per pair.
-// Round 3 sorted the pairs instead from 6 M pairs on (13 launches, 1.1 ms at 512^3 against 0.5 ms now); CFX_FACET_SORT=1
-// keeps that path.
+// (Round 3 sorted the pairs instead from 6 M pairs on: 13 launches, 1.1 ms at 512^3 against 0.5 ms now.)
 constexpr int kFacetMaxNd = 10;
 __host__ __device__ inline int facet_units_per_block(int nd) { return kAdjRun / nd < kBlock ? kAdjRun / nd : kBlock; }
 
@@ -734,53 +732,6 @@ __global__ void __launch_bounds__(kBlock) facet_dof_fill_kernel(DevN nf_d, const
 #pragma unroll
   for (int j = 0; j < kFacetMaxNd; ++j)
     if (key[j] >= 0) facets[offs[key[j]] + s_cnt[slot[j]] + rank[j]] = f;
-}
-
-// dof -> facets incidence by sorting: one (special-row position, facet) pair per dof of a facet's two cells (a dof
-// of both cells once: the cell-1 copy gets the sentinel key `nkeys`, which sorts behind everything).  A stable radix
-// sort over the few key bits replaces ~35 M returning integer atomics on ~2 M counters (count + fill passes) and
-// leaves every list in ascending facet order, whatever the schedule.
-__global__ void __launch_bounds__(kBlock) facet_dof_pairs_kernel(DevN nf_d, const int32_t* __restrict__ rows,
-                                                                 const int32_t* __restrict__ dofmap, int nd,
-                                                                 const int32_t* __restrict__ pos, int32_t nkeys,
-                                                                 int32_t* __restrict__ keys, int32_t* __restrict__ vals)
-{
-  const int64_t nf = dev_n(nf_d);
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= nf * 2 * nd)
-  {
-    // (a facet list shorter than its capacity: the sort runs over the capacity, the tail sorts behind everything)
-    if (i < nf_d.cap * 2 * nd) { keys[i] = nkeys; vals[i] = 0; }
-    return;
-  }
-  const int64_t f = i / (2 * nd);
-  const int k = (int)(i - f * 2 * nd);
-  const int64_t c = rows[4 * f + (k < nd ? 0 : 2)];
-  const int32_t dof = dofmap[c * nd + (k < nd ? k : k - nd)];
-  bool skip = false;
-  if (k >= nd)
-  {
-    const int64_t c0 = rows[4 * f];
-    for (int j = 0; j < nd; ++j) skip = skip || dofmap[c0 * nd + j] == dof;
-  }
-  keys[i] = skip ? nkeys : pos[dof];
-  vals[i] = (int32_t)f;
-}
-
-// offsets[k] = first sorted position whose key is >= k (k = 0 .. nkeys)
-__global__ void __launch_bounds__(kBlock) sorted_key_offsets_kernel(DevN nkeys_d, int64_t n, const int32_t* __restrict__ keys,
-                                                                    int64_t* __restrict__ offsets)
-{
-  const int64_t nkeys = dev_n(nkeys_d);
-  const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (k > nkeys) return;
-  int64_t lo = 0, hi = n;
-  while (lo < hi)
-  {
-    const int64_t mid = (lo + hi) >> 1;
-    if (keys[mid] < (int32_t)k) lo = mid + 1; else hi = mid;
-  }
-  offsets[k] = lo;
 }
 
 // sort each listed dof's facet list so the gather order is reproducible
@@ -2234,7 +2185,6 @@ cfx_row_plan& row_plan(cfx_form_s* a)
   const cfx_cut_s* bulk_cut = nullptr;
   int bulk_value = 0;
   {
-    const char* be = getenv("CFX_BULK_ROWS");
     const void* list = nullptr;
     int64_t list_n = 0;
     bool one_list = true;
@@ -2256,7 +2206,7 @@ cfx_row_plan& row_plan(cfx_form_s* a)
     // between two vertices: cfx_space_s::dof_verts)
     const bool p1 = space_stencil(V).usable && V->bs == 1 && (nd == 4 || nd == 3);
     const bool p2 = V->degree == 2 && (nd == 10 || nd == 6) && nd == (V->mesh->tdim == 3 ? 10 : 6);
-    const ListProvenance* pv = (!(be && be[0] == '0') && one_list && list && (p1 || p2)) ? provenance_lookup(list) : nullptr;
+    const ListProvenance* pv = (env_on<Sw::BULK_ROWS>() && one_list && list && (p1 || p2)) ? provenance_lookup(list) : nullptr;
     const int64_t nvert = V->mesh->nnodes;
     if (pv && pv->n == list_n && pv->cut->gen == pv->gen && pv->cut->mesh == V->mesh && pv->cut->ls_dofmap.p == V->mesh->conn.p
         && pv->cut->ls_ndofs == nvert && pv->cut->codes0.n == nvert && pv->cut->touch_valid && pv->cut->touch0.n == nvert
@@ -2508,8 +2458,6 @@ cfx_row_plan& row_plan(cfx_form_s* a)
   Count n_plain_all;
   // counters of the dof -> facets incidence (zeroed by the kernel that writes the row lists)
   DevArray<int32_t> fcount;
-  const bool facets_by_sort = [&]() { const char* fs = getenv("CFX_FACET_SORT"); return fs && fs[0] == '1'; }()
-                              && nf_cap * 2 * nd < 2147483647LL;
   {
     const int64_t ntiles = (V->ndofs + kByteTile - 1) / kByteTile;
     DevArray<int64_t> tcounts(ntiles), toffs(ntiles + 1);
@@ -2536,7 +2484,7 @@ cfx_row_plan& row_plan(cfx_form_s* a)
     cp.finish(tot);
     plan_flags = (int)tot[3].cap();
     const bool want_plain = space_stencil(V).lists;
-    if (getenv("CFX_PLAN_DEBUG"))
+    if (env_present<Sw::PLAN_DEBUG>())
       fprintf(stderr, "cutfemx_amd: plan rows special %lld plain %lld of %lld dofs\n", (long long)tot[0].cap(),
               (long long)tot[1].cap(), (long long)V->ndofs);
     P.n_special_rows = tot[0];
@@ -2548,7 +2496,7 @@ cfx_row_plan& row_plan(cfx_form_s* a)
     P.special_rows.alloc(tot[0].cap());
     if (want_plain) P.plain_rows.alloc(tot[1].cap());
     if (nf_cap > 0) P.special_pos.alloc(V->ndofs);
-    if (nf_cap > 0 && !facets_by_sort) fcount.alloc(tot[0].cap());
+    if (nf_cap > 0) fcount.alloc(tot[0].cap());
     if (chain.state)
       launch("plan_row_lists", plan_row_lists_chained_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, V->ndofs,
              P.rowmark.p, special.p, P.active_rows.p, P.special_rows.p, want_plain ? P.plain_rows.p : (int32_t*)nullptr,
@@ -2566,50 +2514,23 @@ cfx_row_plan& row_plan(cfx_form_s* a)
   if (nf_cap > 0)
   {
     // dof -> facets incidence of the rows that have facets (all of them special; special_pos came with the row lists)
-    const char* fs = getenv("CFX_FACET_SORT");
     const int64_t npairs = nf_cap * 2 * nd;
     // count + scan + fill with integer atomics combined per workgroup in LDS: 5 launches where the radix sort of
-    // rounds 2-3 takes 13 (a kernel boundary costs ~10 us on this chip, profiles/r04_launch_gaps.txt).  CFX_FACET_SORT=1
-    // keeps the sort (every list then comes out in ascending facet order without the deterministic mode's list sort).
-    (void)fs;
-    if (facets_by_sort && ns_cap < 2147483647LL)
-    {
-      // (lengths still in HBM: the sort covers the capacity of the pair list, pairs behind the last facet carry the
-      // sentinel key = the capacity of the special-row list, which no row position reaches)
-      DevArray<int32_t> keys(npairs), vals(npairs), keys_out(npairs);
-      P.d2f.alloc(npairs); // the sorted values: the entries behind the last offset (sentinel keys) are never read
-      launch("facet_dof_pairs", facet_dof_pairs_kernel, grid_for(npairs), dim3(kBlock), 0, P.nfacets, P.facet_rows.p,
-             V->dofmap.p, nd, P.special_pos.p, (int32_t)ns_cap, keys.p, vals.p);
-      int bits = 1;
-      while ((1ll << bits) <= ns_cap) ++bits; // keys 0 .. ns_cap (the sentinel)
-      size_t tmp_bytes = 0;
-      CFX_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.p, keys_out.p, vals.p, P.d2f.p, (size_t)npairs, 0, bits,
-                                        ctx().stream));
-      DevArray<uint8_t> tmp((int64_t)tmp_bytes);
-      CFX_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, keys.p, keys_out.p, vals.p, P.d2f.p, (size_t)npairs, 0, bits,
-                                        ctx().stream));
-      P.d2f_offsets.alloc(ns_cap + 1);
-      launch("facet_dof_offsets", sorted_key_offsets_kernel, grid_for(ns_cap + 1), dim3(kBlock), 0,
-             P.n_special_rows, npairs, keys_out.p, P.d2f_offsets.p);
-      P.d2f_sorted = true;
-    }
-    else
-    {
-      // (lengths may still be in HBM: the counters cover the capacity of the special-row list -- the tail stays zero --,
-      // the facet list is sized by its upper bound, one entry per (facet, dof of its two cells) pair; the fill reuses
-      // the counters as cursors counting DOWN, so that they need no second zero fill)
-      if (fcount.n != ns_cap || !fcount.p) { fcount.alloc(ns_cap); fcount.zero(); }
-      require(nd <= kFacetMaxNd, CFX_ERR_RUNTIME, "dof -> facets incidence: more than 10 dofs per cell");
-      const int per = facet_units_per_block(nd);
-      const dim3 run_grid((unsigned)((2 * nf_cap + per - 1) / per));
-      launch("facet_dof_count", facet_dof_count_kernel, run_grid, dim3(kBlock), 0, P.nfacets,
-             P.facet_rows.p, V->dofmap.p, nd, P.special_pos.p, fcount.p, ns_cap, step_poison());
-      P.d2f_offsets.alloc(ns_cap + 1);
-      exclusive_scan(fcount.p, P.d2f_offsets.p, ns_cap);
-      P.d2f.alloc(npairs);
-      launch("facet_dof_fill", facet_dof_fill_kernel, run_grid, dim3(kBlock), 0, P.nfacets,
-             P.facet_rows.p, V->dofmap.p, nd, P.special_pos.p, P.d2f_offsets.p, fcount.p, P.d2f.p, ns_cap, step_poison());
-    }
+    // rounds 2-3 took 13 (a kernel boundary costs ~10 us on this chip, profiles/r04_launch_gaps.txt)
+    // (lengths may still be in HBM: the counters cover the capacity of the special-row list -- the tail stays zero --,
+    // the facet list is sized by its upper bound, one entry per (facet, dof of its two cells) pair; the fill reuses
+    // the counters as cursors counting DOWN, so that they need no second zero fill)
+    if (fcount.n != ns_cap || !fcount.p) { fcount.alloc(ns_cap); fcount.zero(); }
+    require(nd <= kFacetMaxNd, CFX_ERR_RUNTIME, "dof -> facets incidence: more than 10 dofs per cell");
+    const int per = facet_units_per_block(nd);
+    const dim3 run_grid((unsigned)((2 * nf_cap + per - 1) / per));
+    launch("facet_dof_count", facet_dof_count_kernel, run_grid, dim3(kBlock), 0, P.nfacets,
+           P.facet_rows.p, V->dofmap.p, nd, P.special_pos.p, fcount.p, ns_cap, step_poison());
+    P.d2f_offsets.alloc(ns_cap + 1);
+    exclusive_scan(fcount.p, P.d2f_offsets.p, ns_cap);
+    P.d2f.alloc(npairs);
+    launch("facet_dof_fill", facet_dof_fill_kernel, run_grid, dim3(kBlock), 0, P.nfacets,
+           P.facet_rows.p, V->dofmap.p, nd, P.special_pos.p, P.d2f_offsets.p, fcount.p, P.d2f.p, ns_cap, step_poison());
   }
   // rank structure of every uncut entity list: entity index of cell c =
   // rank[c/64] + popcount(bits[c/64] below c), two cached loads instead of a
@@ -2648,8 +2569,7 @@ cfx_row_plan& row_plan(cfx_form_s* a)
              (uint8_t)(1u << slot), reinterpret_cast<unsigned long long*>(P.std_bits[slot].p), pop.p, tiles);
     exclusive_scan(pop.p, P.std_rank[slot].p, nwords);
   }
-  const char* det = getenv("CFX_DETERMINISTIC");
-  if (nf_cap > 0 && det && det[0] == '1' && !P.d2f_sorted)
+  if (nf_cap > 0 && env_is<Sw::DETERMINISTIC>('1'))
   {
     // reproducible gather order (the lists were filled through an atomic cursor)
     launch("plan_sort_d2f", seg_sort_kernel, grid_for(ns_cap), dim3(kBlock), 0, P.n_special_rows,
@@ -2669,14 +2589,12 @@ const Stencil& space_stencil(cfx_space_s* V)
   Stencil& S = V->stencil;
   if (S.built) return S;
   S.built = true;
-  const char* env = getenv("CFX_STENCIL");
-  if (env && env[0] == '0') return S;
+  if (!env_on<Sw::STENCIL>()) return S;
   // P1 scalar space on the geometry dofmap (dofs are mesh vertices): lists + slots; every other space (degree 2,
   // vector-valued, DG): the neighbour lists alone, which is what the sparsity of the plain rows needs
   if (V->degree != 1 || V->bs != 1 || V->ndofs_cell > 4 || V->dofmap.p != V->mesh->conn.p || V->ndofs != V->mesh->nnodes)
   {
-    const char* le = getenv("CFX_STENCIL_LISTS");
-    if (le && le[0] == '0') return S;
+    if (!env_on<Sw::STENCIL_LISTS>()) return S;
     const Adjacency& adj = V->dof_cells();
     PatArgs A{};
     A.n_active = V->ndofs; A.active_rows = nullptr; A.all_cells = 1;
@@ -2715,8 +2633,7 @@ const Stencil& space_stencil(cfx_space_s* V)
     size_t live_b = 0, cached_b = 0, peak_b = 0;
     device_memory_stats(live_b, cached_b, peak_b);
     const size_t need = (size_t)V->ndofs * 64 * sizeof(int32_t);
-    const char* sv = getenv("CFX_STENCIL_STAGED");
-    if (need < (free_b + cached_b) / 3 && !(sv && sv[0] == '0')) { staged.alloc(V->ndofs * 64); A.tmp = staged.p; }
+    if (need < (free_b + cached_b) / 3 && env_on<Sw::STENCIL_STAGED>()) { staged.alloc(V->ndofs * 64); A.tmp = staged.p; }
   }
   launch("stencil_rows", pattern_rows_kernel<4, 64>, wave_grid((V->ndofs + 15) / 16), dim3(kWave), 0, A);
   if (read_scalar(overflow.p)) return S; // a vertex with more than 63 neighbours: keep the hashed paths
@@ -2754,8 +2671,7 @@ const Stencil& space_stencil_tiles(cfx_space_s* V)
   Stencil& S = const_cast<Stencil&>(space_stencil(V));
   if (S.tiles_built || !S.usable) return S;
   S.tiles_built = true;
-  const char* env = getenv("CFX_TILES");
-  if (env && env[0] == '0') return S;
+  if (!env_on<Sw::TILES>()) return S;
   const Adjacency& adj = V->dof_cells();
   const int64_t ntiles = (V->ndofs + kRowTile - 1) / kRowTile;
   DevArray<int32_t> counts(ntiles);
@@ -2769,8 +2685,7 @@ const Stencil& space_stencil_tiles(cfx_space_s* V)
   {
     const int64_t need = ntiles * kTileStage * (int64_t)sizeof(int32_t);
     const int64_t perm = (((int64_t)sizeof(uint16_t) * S.nbr.n + 255) & ~255LL);     // st_loc goes in front of it
-    const char* sv = getenv("CFX_STENCIL_STAGED");
-    const bool on = !(sv && sv[0] == '0');
+    const bool on = env_on<Sw::STENCIL_STAGED>();
     if (on && S.arena.p && S.arena_used + perm + need <= S.arena.n)
     {
       // (the tail of the arena; the permanent tables grow from the front and are checked against it below)
@@ -2917,8 +2832,7 @@ __global__ void __launch_bounds__(kBlock) lattice_clear_kernel(int64_t ndofs, ui
 
 bool lattice_rows_on()
 {
-  const char* env = getenv("CFX_LATTICE_ROWS");
-  return !(env && env[0] == '0');
+  return env_on<Sw::LATTICE_ROWS>();
 }
 
 const Stencil& space_lattice(cfx_space_s* V)
@@ -3037,8 +2951,7 @@ const Stencil& space_stencil_slotn(cfx_space_s* V)
   Stencil& S = const_cast<Stencil&>(space_stencil(V));
   if (S.slotn_built) return S;
   S.slotn_built = true;
-  const char* env = getenv("CFX_P2_PLAIN");
-  if ((env && env[0] == '0') || !S.lists || S.usable || V->degree != 2 || V->ndofs_cell > 10 || S.max_len > 255)
+  if (!env_on<Sw::P2_PLAIN>() || !S.lists || S.usable || V->degree != 2 || V->ndofs_cell > 10 || S.max_len > 255)
     return S;
   const Adjacency& adj = V->dof_cells();
   S.slotn.alloc(adj.cells.n * 12);
@@ -3432,8 +3345,7 @@ const VecBlocks& space_vec_blocks(cfx_space_s* V)
   VecBlocks& S = V->vblocks;
   if (S.built) return S;
   S.built = true;
-  const char* env = getenv("CFX_VEC_BLOCKS");
-  if (env && env[0] == '0') return S;
+  if (!env_on<Sw::VEC_BLOCKS>()) return S;
   const int nd = V->ndofs_cell;
   const int64_t nc = V->mesh->ncells;
   if (V->bs != 1 || nc == 0) return S;
@@ -3648,8 +3560,7 @@ static std::vector<int> pattern_form_key(const cfx_form_s* a, bool& ok)
 
 bool pattern_reuse_ok(cfx_form_s* a)
 {
-  const char* e = getenv("CFX_PATTERN_REUSE");
-  if (e && e[0] == '0') return false;
+  if (!env_on<Sw::PATTERN_REUSE>()) return false;
   cfx_space_s* V = a->V;
   const cfx_pattern_cache& pc = V->pcache;
   bool ok = true;
@@ -3660,14 +3571,13 @@ bool pattern_reuse_ok(cfx_form_s* a)
 // the pattern just built becomes the space's previous pattern
 void pattern_remember(cfx_form_s* a, cfx_pattern_s* P)
 {
-  const char* e = getenv("CFX_PATTERN_REUSE");
   cfx_space_s* V = a->V;
   cfx_row_plan& plan = row_plan(a);
   const Stencil& st = space_stencil(V);
   bool ok = true;
   const std::vector<int> key = pattern_form_key(a, ok);
   // (the stencil path -- P1 on the geometry dofmap -- describes its rows by masks and has no use for the cache)
-  if ((e && e[0] == '0') || st.usable || !plan.any_cells || !ok || a->rectangular()) return;
+  if (!env_on<Sw::PATTERN_REUSE>() || st.usable || !plan.any_cells || !ok || a->rectangular()) return;
   plan_cell_signature(a);
   cfx_pattern_cache& pc = V->pcache;
   pc.drop();
@@ -3818,7 +3728,7 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
     }
     rows_d = dirty_rows.p;
     P->n_reused_rows = n_clean;
-    if (getenv("CFX_PLAN_DEBUG"))
+    if (env_present<Sw::PLAN_DEBUG>())
       fprintf(stderr, "cutfemx_amd: pattern reuse: %lld of %lld hashed rows copy their columns\n", (long long)n_clean, (long long)n_h);
   }
   PatArgs S{};
@@ -3937,7 +3847,7 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
   if (!deferred) P->max_row_len = plan.n_active_rows.cap() > 0 ? read_scalar(maxlen.p) : 1;
   if (any_full) P->max_row_len = std::max(P->max_row_len, st.max_len); // a copied row is at most the longest static list
   if (reuse && n_clean > 0) P->max_row_len = std::max(P->max_row_len, read_scalar(reuse_maxlen.p)); // ... or of the previous pattern
-  if (getenv("CFX_PLAN_DEBUG")) fprintf(stderr, "cutfemx_amd: pattern max row length %d (static lists %d)\n", P->max_row_len, st.max_len);
+  if (env_present<Sw::PLAN_DEBUG>()) fprintf(stderr, "cutfemx_amd: pattern max row length %d (static lists %d)\n", P->max_row_len, st.max_len);
   P->indptr.alloc(P->nrows + 1);
   {
     const int64_t ntiles = (P->nrows + kTile - 1) / kTile;
@@ -4106,8 +4016,7 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
           ++n_std;
           closed = closed && I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0;
         }
-      const char* cf = getenv("CFX_P2_CLOSED");
-      if (n_std == 1 && closed && a->rank == 2 && !(cf && cf[0] == '0') && space_stencil_slotn(V).slotn_ok)
+      if (n_std == 1 && closed && a->rank == 2 && env_on<Sw::P2_CLOSED>() && space_stencil_slotn(V).slotn_ok)
       {
         DevArray<int32_t> pos;
         P->n_full_rows = compact("pattern_full_rows", n_plain_x, FlagSet8{full.p}, pos);
@@ -4137,7 +4046,7 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
            base_rows, P->mid_rows.p);
     launch("pattern_map_rows", map_rows_kernel, grid_for(P->n_long_rows), dim3(kBlock), 0, P->n_long_rows,
            base_rows, P->long_rows.p);
-    if (getenv("CFX_PLAN_DEBUG"))
+    if (env_present<Sw::PLAN_DEBUG>())
       fprintf(stderr, "cutfemx_amd: hashed row classes: <= 64 columns %lld, <= 128 %lld, longer %lld\n",
               (long long)P->n_short_rows, (long long)P->n_mid_rows, (long long)P->n_long_rows);
     P->split_plan = plan.serial;

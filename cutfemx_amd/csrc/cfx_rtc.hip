@@ -741,8 +741,7 @@ void module_launch(hipFunction_t fn, int64_t n, void* args, void* coef_args = nu
   const unsigned grid = (unsigned)blocks;
   Context& c = ctx();
   c.last_launch = "user_integrand";
-  static const bool trace = getenv("CFX_LAUNCH_TRACE") != nullptr;
-  if (trace) fprintf(stderr, "cutfemx_amd: launch user_integrand grid %u\n", grid);
+  if (env_present_once<Sw::LAUNCH_TRACE>()) fprintf(stderr, "cutfemx_amd: launch user_integrand grid %u\n", grid);
   if (c.profile)
   {
     hipEvent_t e0 = c.get_event(), e1 = c.get_event();

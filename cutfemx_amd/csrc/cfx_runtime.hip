@@ -127,9 +127,9 @@ int64_t& sync_counter()
 {
   static int64_t n = 0;
   static const bool report = []() {
-    const char* e = getenv("CFX_COUNT_SYNC");
-    if (e && e[0] == '2') ctx().trace_sync = true;
-    if (e && (e[0] == '1' || e[0] == '2')) atexit([]() { fprintf(stderr, "cutfemx_amd: %lld size read-backs\n", (long long)sync_counter()); });
+    const char e = env_char_once<Sw::COUNT_SYNC>();
+    if (e == '2') ctx().trace_sync = true;
+    if (e == '1' || e == '2') atexit([]() { fprintf(stderr, "cutfemx_amd: %lld size read-backs\n", (long long)sync_counter()); });
     return true;
   }();
   (void)report;
@@ -184,8 +184,7 @@ std::map<std::string, StepHistory>& histories()
 }
 bool step_debug()
 {
-  static const bool on = getenv("CFX_STEP_DEBUG") != nullptr;
-  return on;
+  return env_present_once<Sw::STEP_DEBUG>();
 }
 double g_margin = 1.03125; // capacity = previous count x margin + slack
 int64_t g_slack = 256;
@@ -561,7 +560,7 @@ void* dev_alloc(size_t bytes)
     return p;
   }
   void* p = nullptr;
-  static const bool trace = getenv("CFX_ALLOC_TRACE") != nullptr; // every hipMalloc of the block cache, with its duration
+  const bool trace = env_present_once<Sw::ALLOC_TRACE>(); // every hipMalloc of the block cache, with its duration
   const auto t0 = std::chrono::steady_clock::now();
   hipError_t e = hipMalloc(&p, want);
   if (trace)
@@ -870,6 +869,9 @@ ChainState chain_state(int64_t ntiles)
   return ch;
 }
 
+// longest scan (in tiles) that runs as one chained launch
+static int64_t scan_chained_max() { return env_int_once<Sw::SCAN_CHAINED_TILES>(8192); }
+
 template <typename Tin, typename Tout>
 static void scan_impl(const Tin* in, Tout* out, int64_t n, CountPlan* plan = nullptr)
 {
@@ -885,7 +887,7 @@ static void scan_impl(const Tin* in, Tout* out, int64_t n, CountPlan* plan = nul
   // chained up to 16 M elements (one launch instead of three to five: what matters for the many
   // short scans of a step and for the slabs of a multi-GPU run); longer arrays keep the three-kernel
   // form, whose tiles never wait on each other (measured at 135 M elements: 0.60 vs 0.75 ms)
-  static const int64_t chained_max = getenv("CFX_SCAN_CHAINED_TILES") ? atoll(getenv("CFX_SCAN_CHAINED_TILES")) : 8192;
+  const int64_t chained_max = scan_chained_max();
   if (ntiles > 1 && ntiles <= chained_max)
   {
     ChainState ch = chain_state(ntiles);
@@ -921,10 +923,8 @@ template <typename Tin, typename Tout>
 static void scan_pair_impl(const Tin* inA, Tout* outA, const Tin* inB, Tout* outB, int64_t n, CountPlan* plan)
 {
   const int64_t ntiles = (n + kTile - 1) / kTile;
-  static const int64_t chained_max = getenv("CFX_SCAN_CHAINED_TILES") ? atoll(getenv("CFX_SCAN_CHAINED_TILES")) : 8192;
-  static const bool off = getenv("CFX_SCAN_PAIRS") && getenv("CFX_SCAN_PAIRS")[0] == '0';
   constexpr int64_t kPairWords = 1 << 16;
-  if (off || n == 0 || ntiles > chained_max || 2 * ntiles + 1 > kPairWords / 4)
+  if (n == 0 || ntiles > scan_chained_max() || 2 * ntiles + 1 > kPairWords / 4)
   {
     scan_impl<Tin, Tout>(inA, outA, n, nullptr);
     scan_impl<Tin, Tout>(inB, outB, n, plan);
@@ -968,26 +968,10 @@ void exclusive_scan(const int64_t* in, int64_t* out, int64_t n, CountPlan* after
 
 // ---------------------------------------------------------------------------
 // incidence inversion: map[ncells][width] (item ids) -> item -> cells (CSR).
-// Counting sort with integer atomics, then each segment is sorted so the
+// Counting sort with integer atomics (a count pass, a fill pass through a cursor), then each segment is sorted so the
 // result does not depend on the atomic arrival order.
 // ---------------------------------------------------------------------------
-__global__ void adj_count_kernel(const int32_t* __restrict__ map, int64_t nentries, int32_t* counts)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nentries) atomicAdd(&counts[map[i]], 1);
-}
-
-__global__ void adj_fill_kernel(const int32_t* __restrict__ map, int64_t nentries, int width,
-                                const int64_t* __restrict__ offsets, int32_t* cursor, int32_t* cells)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nentries) return;
-  const int32_t item = map[i];
-  const int32_t pos = atomicAdd(&cursor[item], 1);
-  cells[offsets[item] + pos] = (int32_t)(i / width);
-}
-
-// The same two passes with the atomics of a workgroup combined in LDS first.  Consecutive cells of a mesh share most
+// Both passes combine the atomics of a workgroup in LDS first.  Consecutive cells of a mesh share most
 // of their items (a vertex of a Kuhn mesh sits in 24 tets, about ten of them in the same run of 256 cells), and a
 // global integer atomic is a memory-side read-modify-write of its own: 3.2 G of them were 58 + 77 ms of the 512^3
 // setup.  A workgroup takes kAdjRun consecutive entries, counts them per distinct item in an LDS hash table
@@ -1088,18 +1072,14 @@ void build_adjacency(const int32_t* map, int64_t ncells, int width, int64_t nite
   const int64_t nentries = ncells * width;
   DevArray<int32_t> counts(nitems);
   counts.zero();
-  const char* av = getenv("CFX_ADJ_LDS"); // '0': one global atomic per entry (the form of rounds 1-3)
-  const bool lds = !(av && av[0] == '0');
   const dim3 run_grid((unsigned)((nentries + kAdjRun - 1) / kAdjRun));
   require((nentries + kAdjRun - 1) / kAdjRun < 2147483647LL, CFX_ERR_RUNTIME, "grid too large");
-  if (lds) launch("adj_count", adj_count_lds_kernel, run_grid, dim3(kBlock), 0, map, nentries, counts.p);
-  else launch("adj_count", adj_count_kernel, grid_for(nentries), dim3(kBlock), 0, map, nentries, counts.p);
+  launch("adj_count", adj_count_lds_kernel, run_grid, dim3(kBlock), 0, map, nentries, counts.p);
   adj.offsets.alloc(nitems + 1);
   exclusive_scan(counts.p, adj.offsets.p, nitems);
   adj.cells.alloc(nentries);
   counts.zero();
-  if (lds) launch("adj_fill", adj_fill_lds_kernel, run_grid, dim3(kBlock), 0, map, nentries, width, adj.offsets.p, counts.p, adj.cells.p);
-  else launch("adj_fill", adj_fill_kernel, grid_for(nentries), dim3(kBlock), 0, map, nentries, width, adj.offsets.p, counts.p, adj.cells.p);
+  launch("adj_fill", adj_fill_lds_kernel, run_grid, dim3(kBlock), 0, map, nentries, width, adj.offsets.p, counts.p, adj.cells.p);
   launch("adj_sort", adj_sort_kernel, dim3((unsigned)((nitems + 63) / 64)), dim3(64), 0, nitems, adj.offsets.p, adj.cells.p);
   adj.built = true;
   publish_across_lanes();
@@ -1187,8 +1167,7 @@ void dev_fill(void* p, int byte, size_t bytes)
   }
   const unsigned b = (unsigned)byte & 0xffu, word = b | (b << 8) | (b << 16) | (b << 24);
   const int64_t n16 = (int64_t)(bytes / 16);
-  static const bool trace = getenv("CFX_LAUNCH_TRACE") != nullptr;
-  if (trace) fprintf(stderr, "cutfemx_amd: fill of %zu bytes\n", bytes);
+  if (env_present_once<Sw::LAUNCH_TRACE>()) fprintf(stderr, "cutfemx_amd: fill of %zu bytes\n", bytes);
   launch("fill", fill16_kernel, grid_for(std::max<int64_t>(n16, 1), kBlock * 4), dim3(kBlock), 0,
          static_cast<unsigned char*>(p), bytes, word);
 }
@@ -1300,8 +1279,7 @@ int cfx_step_begin(const char* key)
   st.serial = ++step_counter;
   st.key = key ? key : "";
   st.active = true;
-  const char* off = getenv("CFX_STEP_SPECULATE");
-  st.spec = histories()[st.key].valid && !(off && off[0] == '0');
+  st.spec = histories()[st.key].valid && env_on<Sw::STEP_SPECULATE>();
   // poison word + error words of the step (entries below the first slot): one fill
   dev_fill(count_pool(), 0, sizeof(int64_t) * 2 * kCountFirstSlot);
   CFX_API_END

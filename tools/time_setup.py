@@ -1,5 +1,5 @@
 """Setup kernels of the first step at n^3 (mesh-static tables): per-kernel HIP-event times.
-usage: python tools/time_setup.py [n]   (variants through CFX_ADJ_LDS / CFX_C2C, one process each)"""
+usage: python tools/time_setup.py [n]"""
 import ctypes as C
 import os
 import sys
@@ -36,8 +36,7 @@ for i in range(_lib.lib().cfx_profile_count()):
         rows.append((ms.value, name.value.decode(), cnt.value))
 setup = ("adj_", "stencil_", "cell_neighbours", "scan_reduce", "scan_write")
 tot = sum(r[0] for r in rows if r[1].startswith(setup))
-print(f"n={n} first step {1e3 * (t1 - t0):.1f} ms, setup kernels {tot:.1f} ms, nnz {A.nnz}  "
-      f"[CFX_ADJ_LDS={os.environ.get('CFX_ADJ_LDS', '')} CFX_C2C={os.environ.get('CFX_C2C', '')}]")
+print(f"n={n} first step {1e3 * (t1 - t0):.1f} ms, setup kernels {tot:.1f} ms, nnz {A.nnz}")
 for ms, name, cnt in sorted(rows, reverse=True)[:12]:
     print(f"  {name:28s} {ms:9.3f} ms  x{cnt}")
 # a checksum of the tables' consumers: ghost facets and pattern must not depend on the variant
