@@ -661,6 +661,17 @@ struct Stencil
   // taken", cfx_space_lattice_rows): nothing in the assembly reads it.  It costs the streaming role one global atomic
   // per block and launch (at most 4096).
   DevArray<unsigned long long> lat_written;
+  // Closed-form series source term on the lattice rows (cfx::lattice_source_moments, 3-D): the vertex star of
+  // lat_rstar as read back once -- per incident cell the four fl(x_v - x_r*) and the local index of r* -- and, per
+  // quadrature degree, the eight moments T[sigma] of that star (bit d of sigma: sin(pi delta_d) instead of cos).
+  // lat_src_state: 0 not read yet, 1 star on the host, -1 no such star (not 3-D, more than kLatStarCells cells).
+  // lat_src_written: rows written from the closed form so far (diagnostics only, like lat_written).
+  static constexpr int kLatStarCells = 64, kLatSrcDegrees = 9; // (degrees 0 .. CFX_QUAD_MAX_DEGREE)
+  int lat_src_state = 0;
+  std::vector<double> lat_star;                // [cells][13]: 4 x 3 differences, local index
+  double lat_src_T[kLatSrcDegrees][8] = {};
+  bool lat_src_T_built[kLatSrcDegrees] = {};
+  DevArray<unsigned long long> lat_src_written;
   // The single-pass build of the neighbour lists stages 64 columns per dof (34 GB at 512^3).  Giving that block back to
   // the driver made the NEXT large hipMalloc of the process take 1.5 - 2.6 s on this stack (tools/time_malloc.py: 0.2 ms
   // for the first 34 GB, 1.8 s for the same request after a hipFree of 34 GB); left in the block cache it would sit
@@ -693,6 +704,15 @@ __device__ __forceinline__ bool lattice_template_row(unsigned diagpos_raw, unsig
                                                      unsigned inline_bits, unsigned long long full)
 {
   return (diagpos_raw & kLatFlag) != 0 && __popc(umark & inline_bits) == 1 && mask == full;
+}
+// A row of a linear form whose series source term is the closed form in its own coordinates (cfx::lattice_source_moments):
+// it has a slot in the hex-corner staging (vec_t2off != 0: plain, every cell around it carries the mark) and is flagged.
+// The ONE statement of this rule as well: the fold that evaluates the closed form for such rows, the hex kernel that
+// stores no corner sum for them and its filter (a hex is bulk iff all 8 corner rows pass: nobody reads what it would
+// write) must agree row for row, or a row reads a slot that no hex wrote.
+__device__ __forceinline__ bool lattice_source_row(int32_t vec_t2off_r, unsigned diagpos_raw)
+{
+  return vec_t2off_r != 0 && (diagpos_raw & kLatFlag) != 0;
 }
 
 // Cell blocks of a space (mesh-static, built on first use by cfx::space_vec_blocks): B consecutive cells and the
@@ -1018,6 +1038,7 @@ void plan_cut_cells(cfx_form_s* a);                                     // cfx_r
 const Stencil& space_stencil_tiles(cfx_space_s* V);                     // cfx_rowasm.hip
 const Stencil& space_lattice(cfx_space_s* V);                           // cfx_rowasm.hip (Stencil::lat_rows)
 bool lattice_template(cfx_space_s* V);                                  // cfx_gather.hip (Stencil::lat_tmpl)
+const double* lattice_source_moments(cfx_space_s* V, int qdegree);      // cfx_rowasm.hip (Stencil::lat_src_T; null: none)
 bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits);          // cfx_rowasm.hip (cfx_row_plan::lat_tile_first)
 bool space_dof_verts(cfx_space_s* V);                                   // cfx_rowasm.hip (cfx_space_s::dof_verts)
 bool plain_vec_offsets(cfx_form_s* L, uint8_t mark);                    // cfx_rowasm.hip

@@ -1899,6 +1899,17 @@ int cfx_space_lattice_rows(cfx_space_t V, int64_t* n, int64_t* template_rows)
   CFX_API_END
 }
 
+int cfx_space_lattice_source_rows(cfx_space_t V, int64_t* rows)
+{
+  CFX_API_BEGIN
+  require(V && rows, CFX_ERR_INVALID_ARGUMENT, "cfx_space_lattice_source_rows: null argument");
+  *rows = 0;
+  if (V->degree != 1 || V->bs != 1 || !cfx::space_stencil(V).usable) return CFX_OK;
+  const cfx::Stencil& S = cfx::space_lattice(V);
+  if (S.lat_rows > 0 && S.lat_src_written.p) *rows = (int64_t)cfx::read_scalar(S.lat_src_written.p);
+  CFX_API_END
+}
+
 int cfx_space_destroy(cfx_space_t V)
 {
   CFX_API_BEGIN

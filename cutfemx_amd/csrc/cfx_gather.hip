@@ -691,78 +691,130 @@ struct GroupArgs
   int64_t cap;          // corner plane stride of A.t2 (cfx_row_plan::vec_group_cap)
 };
 
-__global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_source_groups_kernel(VecArgs A, GroupArgs G)
+// LATTICE = false: one lane per group entry.
+// LATTICE = true (the closed-form source term is on; diagpos = Stencil::diagpos): most hexes are bulk -- all 8 corner
+// rows take the closed form (lattice_source_row), so nobody reads what the hex would write (its six tets have plain
+// corners only: no per-cell record either).  A per-lane early exit leaves the wavefronts that hold an end of an x-line
+// running the whole body for a handful of lanes (0.97 ms at 512^3 against 0.77 ms: DESIGN.md section 3 round 8);
+// instead every lane evaluates the rule for its own entry (phase A: the corner ids and two words per corner), the
+// block's shell hexes are queued in LDS, and the body runs on the queue in dense wavefronts (phase B) without storing
+// the corner sums of closed-form rows.  The queue order is arbitrary: a hex writes its own slots only.  (The body
+// stands in the kernel itself, as the one pass of a do-loop without LATTICE: as a function of its own the same text
+// spills a register.)
+template <bool LATTICE>
+__global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_source_groups_kernel(VecArgs A, GroupArgs G, const uint8_t* __restrict__ diagpos)
 {
-  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (g >= dev_n(G.ng)) return;
-  const int64_t n = dev_n(A.n), f = G.first[g];
-  int32_t ids[6];
-#pragma unroll
-  for (int m = 0; m < 6; ++m) ids[m] = A.entities[f + m < n ? f + m : n - 1];
-  const int32_t hex = ids[0] / 6;
-  unsigned mask = 0;
-#pragma unroll
-  for (int m = 0; m < 6; ++m)
-    if (f + m < n && ids[m] / 6 == hex) mask |= 1u << (ids[m] - 6 * hex);
-  // the eight corners from tets 0 {0,1,3,7}, 3 {0,2,6,7} and 4 {0,4,5,7}
-  const int4* conn4 = reinterpret_cast<const int4*>(A.conn) + 6 * (int64_t)hex;
-  const int4 r0 = conn4[0], r3 = conn4[3], r4 = conn4[4];
-  const int32_t cv[8] = {r0.x, r0.y, r3.y, r0.z, r4.y, r4.z, r3.z, r0.w};
-  // corners 0 and 7 (in every tet) stay in registers, a tet's middle corners are loaded as it comes.  The tet loop is
-  // not unrolled: the corner sums take a tet's values by selects (the unrolled loop spills at CFX_SOURCE_WAVES = 4)
-  double x0[3], x7[3];
-  load_vertex<3>(A.x, cv[0], x0);
-  load_vertex<3>(A.x, cv[7], x7);
-  // bit k: the row of corner k is plain (its slot is read again, from cache, when the sums are stored)
-  unsigned plain = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) plain |= A.t2off[cv[k]] != 0 ? 1u << k : 0u; // (stored + 1: 0 = the row is not plain)
-  int npts;
-  const double* wts;
-  const double* pts = ref_rule(3, A.qdegree, npts, wts);
-  const double fscale = A.params[1] * ((int)A.params[0] == CFX_F_POISSON_RHS ? 3.0 * kPi * kPi : 1.0);
-  double S[3], C[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) cfx_sincospi(x0[d], S[d], C[d]);
-  double acc[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) acc[k] = 0.0;
-  const int64_t stride = A.out_cells > 0 ? A.out_cells : A.n.cap;
-  // middle corners of tet j (kKuhnTet[j][1], kKuhnTet[j][2]): nibble j of these words
-  constexpr unsigned kMidA = 0x442211u, kMidB = 0x656353u;
-  int j = __builtin_ctz(mask);
-#pragma unroll 1
-  while (true)
+  __shared__ int32_t s_queue[LATTICE ? kBlock : 1];
+  __shared__ int s_n;
+  int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  int q = threadIdx.x, nq = 0;
+  if constexpr (!LATTICE)
   {
-    const unsigned rest = mask & ~((2u << j) - 1u);
-    const int4 row = conn4[j];
-    double x[4][3];
-    load_vertex<3>(A.x, row.y, x[1]);
-    load_vertex<3>(A.x, row.z, x[2]);
-#pragma unroll
-    for (int d = 0; d < 3; ++d) { x[0][d] = x0[d]; x[3][d] = x7[d]; }
-    double be[4];
-    source_vector<3>(x, npts, pts, wts, fscale, be, S, C);
-    const int ka = (int)((kMidA >> (4 * j)) & 0xfu), kb = (int)((kMidB >> (4 * j)) & 0xfu);
-    acc[0] += be[0];
-    acc[7] += be[3];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) acc[k] += k == ka ? be[1] : (k == kb ? be[2] : 0.0);
-    if ((plain & ((1u << ka) | (1u << kb) | 0x81u)) != ((1u << ka) | (1u << kb) | 0x81u))
-    {
-      const int64_t at = A.out_cells > 0 ? 6 * (int64_t)hex + j : f + __popc(mask & ((1u << j) - 1u));
-#pragma unroll
-      for (int i = 0; i < 4; ++i) A.out[(int64_t)i * stride + at] = be[i];
-    }
-    if (!rest) break;
-    j = __builtin_ctz(rest);
+    if (g >= dev_n(G.ng)) return;
   }
-  // (the corner ids again: the rows of tets 0, 3, 4 are in cache; holding them through the loop spills)
-  const int4 s0 = conn4[0], s3 = conn4[3], s4 = conn4[4];
-  const int32_t sv[8] = {s0.x, s0.y, s3.y, s0.z, s4.y, s4.z, s3.z, s0.w};
+  else
+  {
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    if (g < dev_n(G.ng))
+    {
+      const int4* c = reinterpret_cast<const int4*>(A.conn) + 6 * (int64_t)(A.entities[G.first[g]] / 6);
+      const int4 r0 = c[0], r3 = c[3], r4 = c[4];
+      const int32_t cv[8] = {r0.x, r0.y, r3.y, r0.z, r4.y, r4.z, r3.z, r0.w};
+      bool bulk = true;
 #pragma unroll
-  for (int k = 0; k < 8; ++k)
-    if (plain & (1u << k)) A.t2[(int64_t)k * G.cap + A.t2off[sv[k]] - 1] = acc[k];
+      for (int k = 0; k < 8; ++k) bulk = bulk & lattice_source_row(A.t2off[cv[k]], diagpos[cv[k]]);
+      if (!bulk) s_queue[atomicAdd(&s_n, 1)] = (int32_t)threadIdx.x;
+    }
+    __syncthreads();
+    nq = s_n;
+  }
+  do
+  {
+    if constexpr (LATTICE)
+    {
+      if (q >= nq) break;
+      g = (int64_t)blockIdx.x * kBlock + s_queue[q];
+      q += kBlock;
+    }
+    const int64_t n = dev_n(A.n), f = G.first[g];
+    int32_t ids[6];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) ids[m] = A.entities[f + m < n ? f + m : n - 1];
+    const int32_t hex = ids[0] / 6;
+    unsigned mask = 0;
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+      if (f + m < n && ids[m] / 6 == hex) mask |= 1u << (ids[m] - 6 * hex);
+    // the eight corners from tets 0 {0,1,3,7}, 3 {0,2,6,7} and 4 {0,4,5,7}
+    const int4* conn4 = reinterpret_cast<const int4*>(A.conn) + 6 * (int64_t)hex;
+    const int4 r0 = conn4[0], r3 = conn4[3], r4 = conn4[4];
+    const int32_t cv[8] = {r0.x, r0.y, r3.y, r0.z, r4.y, r4.z, r3.z, r0.w};
+    // corners 0 and 7 (in every tet) stay in registers, a tet's middle corners are loaded as it comes.  The tet loop is
+    // not unrolled: the corner sums take a tet's values by selects (the unrolled loop spills at CFX_SOURCE_WAVES = 4)
+    double x0[3], x7[3];
+    load_vertex<3>(A.x, cv[0], x0);
+    load_vertex<3>(A.x, cv[7], x7);
+    // bit k: the row of corner k is plain (its slot is read again, from cache, when the sums are stored)
+    unsigned plain = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) plain |= A.t2off[cv[k]] != 0 ? 1u << k : 0u; // (stored + 1: 0 = the row is not plain)
+    int npts;
+    const double* wts;
+    const double* pts = ref_rule(3, A.qdegree, npts, wts);
+    const double fscale = A.params[1] * ((int)A.params[0] == CFX_F_POISSON_RHS ? 3.0 * kPi * kPi : 1.0);
+    double S[3], C[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) cfx_sincospi(x0[d], S[d], C[d]);
+    double acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.0;
+    const int64_t stride = A.out_cells > 0 ? A.out_cells : A.n.cap;
+    // middle corners of tet j (kKuhnTet[j][1], kKuhnTet[j][2]): nibble j of these words
+    constexpr unsigned kMidA = 0x442211u, kMidB = 0x656353u;
+    int j = __builtin_ctz(mask);
+#pragma unroll 1
+    while (true)
+    {
+      const unsigned rest = mask & ~((2u << j) - 1u);
+      const int4 row = conn4[j];
+      double x[4][3];
+      load_vertex<3>(A.x, row.y, x[1]);
+      load_vertex<3>(A.x, row.z, x[2]);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) { x[0][d] = x0[d]; x[3][d] = x7[d]; }
+      double be[4];
+      source_vector<3>(x, npts, pts, wts, fscale, be, S, C);
+      const int ka = (int)((kMidA >> (4 * j)) & 0xfu), kb = (int)((kMidB >> (4 * j)) & 0xfu);
+      acc[0] += be[0];
+      acc[7] += be[3];
+#pragma unroll
+      for (int k = 1; k < 7; ++k) acc[k] += k == ka ? be[1] : (k == kb ? be[2] : 0.0);
+      if ((plain & ((1u << ka) | (1u << kb) | 0x81u)) != ((1u << ka) | (1u << kb) | 0x81u))
+      {
+        const int64_t at = A.out_cells > 0 ? 6 * (int64_t)hex + j : f + __popc(mask & ((1u << j) - 1u));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) A.out[(int64_t)i * stride + at] = be[i];
+      }
+      if (!rest) break;
+      j = __builtin_ctz(rest);
+    }
+    // (the corner ids again: the rows of tets 0, 3, 4 are in cache; holding them through the loop spills)
+    const int4 s0 = conn4[0], s3 = conn4[3], s4 = conn4[4];
+    const int32_t sv[8] = {s0.x, s0.y, s3.y, s0.z, s4.y, s4.z, s3.z, s0.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+    {
+      // the sum of corner k is stored for a plain row; with LATTICE only where the fold reads it (decided here, from the
+      // row's own words, not carried through the loop as a mask: one more live register spills)
+      if constexpr (LATTICE)
+      {
+        const int32_t off = A.t2off[sv[k]];
+        if (off != 0 && !lattice_source_row(off, diagpos[sv[k]])) A.t2[(int64_t)k * G.cap + off - 1] = acc[k];
+      }
+      else if (plain & (1u << k)) A.t2[(int64_t)k * G.cap + A.t2off[sv[k]] - 1] = acc[k];
+    }
+  } while (LATTICE);
 }
 
 // ---------------------------------------------------------------------------
@@ -3798,6 +3850,10 @@ struct Stage1
   std::vector<DevArray<double>> buffers;
   DevArray<double> t2;      // linear forms, P1: row-ordered staging of the uncut cells (run_vector), else empty
   double* vec_t2 = nullptr;
+  // hex groups with the closed-form source term on the lattice rows (run_vector): Stencil::diagpos and the moments of
+  // the integral's quadrature degree -- the hex kernel and the fold take their roles from this one pointer
+  const uint8_t* lat_src = nullptr;
+  const double* lat_src_T = nullptr;
   bool vec_blocks = false;  // linear forms: the uncut cells go by cell block (run_vector), nothing is staged per cell
   DevArray<double> part;    // ... the partials of the step
 };
@@ -3873,7 +3929,8 @@ void vec_block_partials(cfx_form_s* L, const cfx_integral_dev* Istd, uint8_t mar
 }
 
 template <int TDIM, int DEG>
-void vec_tensors(cfx_form_s* L, const cfx_integral_dev& I, bool runtime, double* out, double* t2 = nullptr, int64_t out_cells = 0)
+void vec_tensors(cfx_form_s* L, const cfx_integral_dev& I, bool runtime, double* out, double* t2 = nullptr, int64_t out_cells = 0,
+                 const uint8_t* lat_src = nullptr)
 {
   cfx_space_s* V = L->V;
   if (user_integrand_known(I.kernel))
@@ -3902,8 +3959,10 @@ void vec_tensors(cfx_form_s* L, const cfx_integral_dev& I, bool runtime, double*
       DevArray<int32_t> first;
       const Count ng = compact_count("source_groups", "vec.source_groups", A.n, GroupHead{A.entities}, first);
       GroupArgs G{first.p, ng.devn(), plan.vec_group_cap};
-      if (ng.cap() > 0)
-        launch("vec_tensors_std", vec_source_groups_kernel, grid_for(ng.cap()), dim3(kBlock), 0, A, G);
+      if (ng.cap() > 0 && lat_src) // (the closed form serves the bulk rows: Stage1::lat_src)
+        launch("vec_tensors_std", vec_source_groups_kernel<true>, grid_for(ng.cap()), dim3(kBlock), 0, A, G, lat_src);
+      else if (ng.cap() > 0)
+        launch("vec_tensors_std", vec_source_groups_kernel<false>, grid_for(ng.cap()), dim3(kBlock), 0, A, G, lat_src);
     }
     else if (source_series_ok<DEG>(V, I))
     {
@@ -4008,7 +4067,8 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
       R.n_std = by_cell ? V->mesh->ncells : n_ent;
       R.std_by_cell = by_cell ? 1 : 0;
       if (a->rank == 2) dump_integral(a, ii, 1, st.buffers.back().p);
-      else if constexpr (BS == 1) vec_tensors<TDIM, DEG>(a, I, false, st.buffers.back().p, st.vec_t2, by_cell ? V->mesh->ncells : 0);
+      else if constexpr (BS == 1)
+        vec_tensors<TDIM, DEG>(a, I, false, st.buffers.back().p, st.vec_t2, by_cell ? V->mesh->ncells : 0, st.lat_src);
     }
     const int64_t n_rules = I.rules ? I.rules->nr.cap() : 0;
     if (n_rules > 0 && combine_cuts)
@@ -4606,24 +4666,89 @@ __global__ void __launch_bounds__(kWave) assemble_vec_plain_kernel(DevN n_plain_
 
 // ... with hex groups (cfx_row_plan::vec_groups): plain row r = rows[i] adds its corner slots k * cap + i, k over the bits
 // of hex_corners[r] in ascending order (one lane per row; a lane's loads and its neighbours' are contiguous)
+// LatticeSource (diagpos set): a row that takes the closed form (lattice_source_row) reads no slot -- its value is
+// fscale * sum_sigma T[sigma] prod_d (sigma_d ? cos : sin)(pi x_r,d), summed in one fixed nested order (z innermost)
+struct LatticeSource
+{
+  const uint8_t* diagpos; // null: every row sums its slots
+  const double* x;
+  double T[8];
+  double field, scale;    // the integral's params[0], params[1]
+  unsigned long long* written;
+};
+
+template <bool LATTICE>
 __global__ void __launch_bounds__(kBlock) assemble_vec_plain_groups_kernel(DevN n_plain_d, const int32_t* __restrict__ rows,
                                                                            const uint8_t* __restrict__ corners,
                                                                            const int32_t* __restrict__ t2off,
                                                                            const double* __restrict__ t2, int64_t cap,
-                                                                           double* __restrict__ b)
+                                                                           double* __restrict__ b, LatticeSource Ls)
 {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= dev_n(n_plain_d) || i >= cap) return;
-  const int64_t r = rows[i];
-  if (t2off[r] == 0) return; // (a plain row whose cells do not all carry the mark: the per-cell records)
-  const unsigned m = corners[r];
-  double v[8];
+  if constexpr (!LATTICE)
+  {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= dev_n(n_plain_d) || i >= cap) return;
+    const int64_t r = rows[i];
+    if (t2off[r] == 0) return; // (a plain row whose cells do not all carry the mark: the per-cell records)
+    const unsigned m = corners[r];
+    double v[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = (m >> k) & 1u ? t2[k * cap + i] : 0.0;
-  double sum = v[0];
+    for (int k = 0; k < 8; ++k) v[k] = (m >> k) & 1u ? t2[k * cap + i] : 0.0;
+    double sum = v[0];
 #pragma unroll
-  for (int k = 1; k < 8; ++k) sum += v[k];
-  b[r] += sum;
+    for (int k = 1; k < 8; ++k) sum += v[k];
+    b[r] += sum;
+  }
+  else
+  {
+    // a grid-stride loop over a capped grid (2048 blocks): the diagnostics counter then costs one atomic per block of
+    // the grid and not one per 256 rows (67 k atomics on one word made this launch 0.78 ms)
+    const int64_t n = min(dev_n(n_plain_d), cap);
+    int n_closed = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock)
+    {
+      const int64_t r = rows[i];
+      const int32_t off = t2off[r];
+      if (lattice_source_row(off, Ls.diagpos[r]))
+      {
+        double xr[3], S[3], C[3];
+        load_vertex<3>(Ls.x, r, xr);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) cfx_sincospi(xr[d], S[d], C[d]);
+        const double fscale = Ls.scale * ((int)Ls.field == CFX_F_POISSON_RHS ? 3.0 * kPi * kPi : 1.0);
+        double vy[2];
+#pragma unroll
+        for (int sx = 0; sx < 2; ++sx)
+        {
+          double vz[2];
+#pragma unroll
+          for (int sy = 0; sy < 2; ++sy) vz[sy] = fma(Ls.T[sx + 2 * sy + 4], C[2], Ls.T[sx + 2 * sy] * S[2]);
+          vy[sx] = fma(vz[1], C[1], vz[0] * S[1]);
+        }
+        b[r] += fscale * fma(vy[1], C[0], vy[0] * S[0]);
+        ++n_closed;
+      }
+      else if (off != 0)
+      {
+        const unsigned m = corners[r];
+        double v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = (m >> k) & 1u ? t2[k * cap + i] : 0.0;
+        double sum = v[0];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) sum += v[k];
+        b[r] += sum;
+      }
+    }
+    __shared__ int s_closed;
+    if (threadIdx.x == 0) s_closed = 0;
+    __syncthreads();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n_closed += __shfl_xor(n_closed, o, 64);
+    if (threadIdx.x % 64 == 0 && n_closed) atomicAdd(&s_closed, n_closed);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_closed) atomicAdd(Ls.written, (unsigned long long)s_closed);
+  }
 }
 
 // Which way the uncut cells and rules of a linear form reach the rows.  The series source term on a P1 space keeps the
@@ -4680,6 +4805,14 @@ void run_vector(cfx_form_s* L, double* b)
       // CFX_STAGING_NAN=1 (tests): the corner planes start as NaN, so that a slot the fold adds but no hex wrote shows
       // in b whatever the block cache hands out
       if (plan.vec_groups && env_is<Sw::STAGING_NAN>('1')) dev_fill(st.t2.p, 0xff, sizeof(double) * (size_t)(8 * plan.vec_group_cap));
+      // ... and on a lattice mesh the rows whose cells are translates of the representative's take the closed form of
+      // the series source term (hex groups are 3-D, the integral is the series source: cfx::source_groups_ok).
+      // CFX_LATTICE_SOURCE=0: never; CFX_LATTICE_ROWS=0 (no flags) switches it off as well
+      if (plan.vec_groups && env_on<Sw::LATTICE_SOURCE>() && space_lattice(L->V).lat_rows > 0)
+      {
+        st.lat_src_T = lattice_source_moments(L->V, L->integrals[plan.cell_slot_integral[slot]].qdegree);
+        if (st.lat_src_T) st.lat_src = space_stencil(L->V).diagpos.p;
+      }
     }
   }
   RowArgs A = prepare<TDIM, DEG>(L, st);
@@ -4710,9 +4843,21 @@ void run_vector(cfx_form_s* L, double* b)
   if (st.vec_t2)
   {
     constexpr int G = CFX_VEC_PLAIN_G;
-    if (plan.vec_groups)
-      launch("assemble_vec_plain", assemble_vec_plain_groups_kernel, grid_for(plan.n_plain_rows.cap()), dim3(kBlock), 0,
-             plan.n_plain_rows, plan.plain_rows.p, L->V->mesh->hex_corners.p, plan.vec_t2off.p, st.vec_t2, plan.vec_group_cap, b);
+    LatticeSource Ls{};
+    if (st.lat_src)
+    {
+      const cfx_integral_dev& I = L->integrals[plan.cell_slot_integral[slot]];
+      Ls.diagpos = st.lat_src; Ls.x = L->V->mesh->x.p; Ls.field = I.params[0]; Ls.scale = I.params[1];
+      for (int s = 0; s < 8; ++s) Ls.T[s] = st.lat_src_T[s];
+      Ls.written = space_stencil(L->V).lat_src_written.p;
+    }
+    if (plan.vec_groups && st.lat_src)
+      launch("assemble_vec_plain", assemble_vec_plain_groups_kernel<true>,
+             dim3(std::min(grid_for(plan.n_plain_rows.cap()).x, 2048u)), dim3(kBlock), 0,
+             plan.n_plain_rows, plan.plain_rows.p, L->V->mesh->hex_corners.p, plan.vec_t2off.p, st.vec_t2, plan.vec_group_cap, b, Ls);
+    else if (plan.vec_groups)
+      launch("assemble_vec_plain", assemble_vec_plain_groups_kernel<false>, grid_for(plan.n_plain_rows.cap()), dim3(kBlock), 0,
+             plan.n_plain_rows, plan.plain_rows.p, L->V->mesh->hex_corners.p, plan.vec_t2off.p, st.vec_t2, plan.vec_group_cap, b, Ls);
     else
       launch("assemble_vec_plain", assemble_vec_plain_kernel<G>,
              dim3((unsigned)((plan.n_plain_rows.cap() + (kWave / G) - 1) / (kWave / G))), dim3(kWave), 0, plan.n_plain_rows,
@@ -5179,7 +5324,8 @@ void prepare_form_tables(cfx_form_s* a)
     int slot = -1, count = 0;
     for (int s = 0; s < plan.n_cell_slots; ++s)
       if (a->integrals[plan.cell_slot_integral[s]].n_entities.cap() > 0) { slot = s; ++count; }
-    if (count == 1) (void)plain_vec_offsets(a, (uint8_t)(1u << slot));
+    if (count == 1 && plain_vec_offsets(a, (uint8_t)(1u << slot)) && plan.vec_groups && env_on<Sw::LATTICE_SOURCE>())
+      (void)lattice_source_moments(V, a->integrals[plan.cell_slot_integral[slot]].qdegree); // (run_vector: the closed form)
   }
 }
 

@@ -9,6 +9,7 @@
 // produces one after the other (assemble_matrix_impl.h:103-188, :462-606) --
 // and the group reduces the items into the row's CSR slots in LDS in item
 // order, so no global atomics are issued and the sums do not depend on timing.
+#include <cmath>
 #include <cstdlib>
 
 
@@ -2869,6 +2870,8 @@ const Stencil& space_lattice(cfx_space_s* V)
   {
     S.lat_written.alloc(1);
     S.lat_written.zero();
+    S.lat_src_written.alloc(1);
+    S.lat_src_written.zero();
     S.lat_rstar = (int64_t)h[1];
     S.lat_sb0 = (int64_t)h[4];
     S.lat_rel = (int)((int64_t)h[5] - (int64_t)h[4]);
@@ -2878,6 +2881,105 @@ const Stencil& space_lattice(cfx_space_s* V)
   S.lat_built = true;
   publish_across_lanes();
   return S;
+}
+
+// the vertex star of row rs: per incident cell t the four fl(x_v - x_rs) (formed as lattice_flag_kernel compares them)
+// and the local index of rs; out[0] = the number of cells, -1 when they do not fit
+__global__ void __launch_bounds__(kWave) lattice_star_kernel(int64_t rs, const int64_t* __restrict__ d2c_off,
+                                                             const int32_t* __restrict__ d2c, const int32_t* __restrict__ conn,
+                                                             const double* __restrict__ x, int max_cells, double* __restrict__ out)
+{
+  const int64_t cb = d2c_off[rs];
+  const int nc = (int)(d2c_off[rs + 1] - cb), t = threadIdx.x;
+  if (t == 0) out[0] = nc <= max_cells ? (double)nc : -1.0;
+  if (t >= nc || nc > max_cells) return;
+  const int64_t c = d2c[cb + t];
+  double* o = out + 1 + 13 * t;
+  int loc = -1;
+  for (int i = 0; i < 4; ++i)
+  {
+    const int64_t v = conn[4 * c + i];
+    if (v == rs) loc = i;
+    for (int d = 0; d < 3; ++d) o[3 * i + d] = x[3 * v + d] - x[3 * rs + d];
+  }
+  o[12] = (double)loc;
+}
+
+const double* quad_points_host(int dim, int degree);  // cfx_quadhost.cpp
+const double* quad_weights_host(int dim, int degree);
+int quad_npoints(int dim, int degree);
+
+// The moments of the closed-form series source term (see lattice_source_row): for f = c prod_d sin(pi x_d) and a lattice
+// row r, every quadrature point of the vertex star sits at x_r + delta with the deltas of the representative row, and
+// sin(pi (x + delta)) = sin(pi x) cos(pi delta) + cos(pi x) sin(pi delta) factors the whole quadrature sum:
+//   b[r] = c sum_sigma T[sigma] prod_d (sigma_d ? cos(pi x_r,d) : sin(pi x_r,d)),
+//   T[sigma] = sum_cells |det| sum_q w_q N_loc(X_q) prod_d (sigma_d ? sin(pi delta_d) : cos(pi delta_d)),  bit d of sigma.
+// Eight mesh-static numbers per quadrature degree, formed on the host in long double from one read-back of the star
+// (mesh-static: not under a speculative step's void guard; the state is set after the copy has arrived).  3-D only.
+const double* lattice_source_moments(cfx_space_s* V, int qdegree)
+{
+  Stencil& S = const_cast<Stencil&>(space_lattice(V));
+  if (S.lat_rows <= 0 || S.lat_src_state < 0 || qdegree < 0 || qdegree > CFX_QUAD_MAX_DEGREE || qdegree >= Stencil::kLatSrcDegrees)
+    return nullptr;
+  if (S.lat_src_state == 0)
+  {
+    if (V->mesh->tdim != 3 || V->dofmap.p != V->mesh->conn.p) { S.lat_src_state = -1; return nullptr; }
+    const Adjacency& adj = V->dof_cells();
+    constexpr int kN = 1 + 13 * Stencil::kLatStarCells;
+    DevArray<double> star(kN);
+    launch("lattice_rows", lattice_star_kernel, dim3(1), dim3(kWave), 0, S.lat_rstar, adj.offsets.p, adj.cells.p,
+           V->mesh->conn.p, V->mesh->x.p, (int)Stencil::kLatStarCells, star.p);
+    static_assert(Stencil::kLatSrcDegrees == CFX_QUAD_MAX_DEGREE + 1, "one set of moments per degree of the tables");
+    std::vector<double> h((size_t)kN); // (6.7 kB, once per space: more than pinned_scratch() holds)
+    CFX_HIP(hipMemcpyAsync(h.data(), star.p, sizeof(double) * (size_t)kN, hipMemcpyDeviceToHost, ctx().stream));
+    CFX_HIP(hipStreamSynchronize(ctx().stream));
+    ++sync_counter();
+    const int nc = (int)h[0];
+    bool ok = nc > 0 && nc <= Stencil::kLatStarCells;
+    for (int t = 0; ok && t < nc; ++t) ok = h[1 + 13 * t + 12] >= 0.0;
+    if (!ok) { S.lat_src_state = -1; return nullptr; }
+    S.lat_star.assign(h.begin() + 1, h.begin() + 1 + 13 * nc);
+    S.lat_src_state = 1;
+    publish_across_lanes();
+  }
+  if (!S.lat_src_T_built[qdegree])
+  {
+    const int npts = quad_npoints(3, qdegree);
+    const double* pts = quad_points_host(3, qdegree);
+    const double* wts = quad_weights_host(3, qdegree);
+    const long double pi = 3.14159265358979323846264338327950288L;
+    long double T[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int nc = (int)(S.lat_star.size() / 13);
+    for (int t = 0; t < nc; ++t)
+    {
+      const double* o = S.lat_star.data() + 13 * t;
+      const int loc = (int)o[12];
+      long double e[3][3];
+      for (int k = 0; k < 3; ++k)
+        for (int d = 0; d < 3; ++d) e[k][d] = (long double)o[3 * (k + 1) + d] - (long double)o[d];
+      const long double det = e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0])
+                              + e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
+      const long double adet = det < 0 ? -det : det;
+      for (int q = 0; q < npts; ++q)
+      {
+        const long double X[3] = {pts[3 * q], pts[3 * q + 1], pts[3 * q + 2]};
+        const long double N = loc == 0 ? 1.0L - X[0] - X[1] - X[2] : X[loc - 1];
+        long double sn[3], cs[3];
+        for (int d = 0; d < 3; ++d)
+        {
+          const long double delta = (long double)o[d] + X[0] * e[0][d] + X[1] * e[1][d] + X[2] * e[2][d];
+          sn[d] = sinl(pi * delta);
+          cs[d] = cosl(pi * delta);
+        }
+        const long double wn = adet * (long double)wts[q] * N;
+        for (int s = 0; s < 8; ++s)
+          T[s] += wn * ((s & 1) ? sn[0] : cs[0]) * ((s & 2) ? sn[1] : cs[1]) * ((s & 4) ? sn[2] : cs[2]);
+      }
+    }
+    for (int s = 0; s < 8; ++s) S.lat_src_T[qdegree][s] = (double)T[s];
+    S.lat_src_T_built[qdegree] = true;
+  }
+  return S.lat_src_T[qdegree];
 }
 
 // first plain row of its tile that does not take the lattice template (see assemble_tiles_plain_kernel: the same test)

@@ -24,6 +24,7 @@
   CFX_SWITCH(STENCIL_STAGED,     first_char, build, "0: two-pass stencil rows and tiles, the build a card short of memory takes (no test provokes that: the only handle on it)") \
   CFX_SWITCH(TILES,              first_char, build, "0: no row tiles") \
   CFX_SWITCH(LATTICE_ROWS,       first_char, build, "0: no lattice flags and no template: every plain row is computed by the tile kernel") \
+  CFX_SWITCH(LATTICE_SOURCE,     first_char, call,  "0: the P1 series source term of the lattice rows hex by hex instead of its closed form per row") \
   CFX_SWITCH(P2_PLAIN,           first_char, build, "0: degree 2 without the slot-record kernel") \
   CFX_SWITCH(P2_CLOSED,          first_char, call,  "0: degree 2 stages uncut tensors instead of closed-form rows") \
   CFX_SWITCH(P2_MOMENTS,         first_char, call,  "0: degree 2 stages cut-cell stiffness tensors instead of moments") \

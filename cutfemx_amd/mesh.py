@@ -218,6 +218,13 @@ class FunctionSpace:
         assembly's count."""
         return self._lattice()[1]
 
+    def lattice_source_rows(self) -> int:
+        """Rows of linear forms written from the closed form of the series source term since the space was created
+        (cfx_space_lattice_source_rows); the difference across an assembly is that assembly's count."""
+        n = C.c_int64(0)
+        _lib.check(_lib.lib().cfx_space_lattice_source_rows(self._h, C.byref(n)))
+        return int(n.value)
+
     @property
     def dofmap(self) -> np.ndarray:
         if hasattr(self, "_host_dofmap"):

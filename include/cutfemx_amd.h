@@ -402,6 +402,13 @@ int cfx_space_static_bytes(cfx_space_t V, int64_t bytes[4]);
  * deterministic kernel computes.  *template_rows (may be NULL) = rows written that way since the space was created:
  * the difference across one cfx_assemble_matrix call is that call's count. */
 int cfx_space_lattice_rows(cfx_space_t V, int64_t* n, int64_t* template_rows);
+/* Rows of linear forms on V written from the closed form of the series source term since the space was created
+ * (diagnostics; the difference across one cfx_assemble_vector call is that call's count).  On a lattice row (see above)
+ * whose cells are all uncut entities of a CFX_L_SOURCE integral with f = c prod_d sin(pi x_d) on a mesh of hex groups,
+ * the quadrature sum of cpp/dolfinx_custom_data/fem/assemble_vector_impl.h over the row's cells factors into eight
+ * mesh-static moments of the representative row's cells times sin / cos of the row's own coordinates; the result
+ * differs from the cell loop's by rounding only.  0 without lattice rows, in 2-D, under CFX_LATTICE_SOURCE=0. */
+int cfx_space_lattice_source_rows(cfx_space_t V, int64_t* rows);
 int cfx_space_destroy(cfx_space_t V);
 
 /* ---- forms: dolfinx_custom_data::fem::Form, Form.h:119-178, built as in
