@@ -31,6 +31,7 @@ K_JUMP = 9
 K_SIP = 10
 K_DIV_TEST, K_DIV_TRIAL = 20, 21
 L_SOURCE, L_NITSCHE_RHS = 101, 102
+M_FIELD, M_L2_DIFF, M_H1_SEMI = 201, 202, 203   # functionals (rank 0): cfx_assemble_scalar
 F_ONE, F_SINPROD, F_POISSON_RHS, F_COEFFICIENT = 0, 1, 2, 3
 
 
@@ -103,7 +104,7 @@ SYMBOLS = [
     "cfx_evaluate_values", "cfx_ghost_penalty_facets", "cfx_interior_facets_for_cells", "cfx_cell_aggregation_create", "cfx_cell_aggregation_view_get",
     "cfx_cell_aggregation_destroy", "cfx_cut_destroy", "cfx_space_create",
     "cfx_space_static_bytes", "cfx_space_lattice_rows", "cfx_space_lattice_source_rows", "cfx_space_destroy", "cfx_form_create", "cfx_form_create2", "cfx_form_destroy", "cfx_form_prepare", "cfx_create_sparsity",
-    "cfx_pattern_view_get", "cfx_pattern_reuse_stats", "cfx_pattern_destroy", "cfx_assemble_matrix", "cfx_assemble_matrix_zeroed", "cfx_assemble_vector",
+    "cfx_pattern_view_get", "cfx_pattern_reuse_stats", "cfx_pattern_destroy", "cfx_assemble_matrix", "cfx_assemble_matrix_zeroed", "cfx_assemble_vector", "cfx_assemble_scalar",
     "cfx_apply_lifting", "cfx_set_bc", "cfx_zero_rows", "cfx_csr_block_merge", "cfx_csr_permute", "cfx_tabulate_entity", "cfx_active_domain", "cfx_active_view", "cfx_deactivate_outside",
     "cfx_active_destroy",
     "cfx_dist_unique_id", "cfx_dist_comm_create", "cfx_dist_comm_create_host", "cfx_dist_comm_create_device", "cfx_dist_comm_info", "cfx_dist_comm_destroy",

@@ -1017,7 +1017,7 @@ struct cfx_form_s
   cfx_space_t V = nullptr;  // test space (the space of a linear form)
   cfx_space_t V1 = nullptr; // trial space: V for square forms, another space for cfx_form_create2 forms
   bool rectangular() const { return V1 != nullptr && V1 != V; }
-  int rank = 2;
+  int rank = 2; // 0: a functional (cfx_assemble_scalar; no row plan)
   std::vector<cfx_integral_dev> integrals;
   std::shared_ptr<cfx_row_plan> plan; // built lazily, possibly shared with another live form
   // complex128 forms: the integrals that share one complex constant as a real form of their own (cfx_c128.hip), kept
@@ -1060,9 +1060,12 @@ int user_integrand_rank(int kernel);
 int user_integrand_kind(int kernel); // 0: cell integrand, 1: interior-facet integrand
 bool user_integrand_two(int kernel);  // registered with cfx_integrand_register2: serves forms between two spaces
 void user_coefficients_check(const cfx_form_s* a, const cfx_integral_dev& I); // the list of I: limits of `w`, compiled shapes
-void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* out, int64_t only_index = -1);
-void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, double* out, int out_mode, int64_t out_stride,
-                 int64_t only_index = -1);
+// (both return the number of 256-entity blocks they launched: a rank-0 form gets one partial sum per block in `out`)
+int64_t user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* out, int64_t only_index = -1);
+int64_t user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, double* out, int out_mode, int64_t out_stride,
+                    int64_t only_index = -1);
+// functionals (cfx_scalar.hip): the contribution of one entity of a rank-0 form into out_dev[0] (cfx_tabulate_entity)
+void functional_entity(const cfx_form_s* M, const cfx_integral_dev& I, int64_t index, int use_rule, double* out_dev);
 } // namespace cfx
 
 struct cfx_pattern_s

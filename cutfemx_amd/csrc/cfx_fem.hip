@@ -1940,7 +1940,7 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
   CFX_API_BEGIN
   ctx().ensure();
   require(V && out && (integrals || n_integrals == 0), CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: null argument");
-  require(rank == 1 || rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: rank must be 1 or 2");
+  require(rank == 0 || rank == 1 || rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: rank must be 0, 1 or 2");
   auto a = std::make_unique<cfx_form_s>();
   a->V = V; a->V1 = V1; a->rank = rank;
   const bool rect = V1 != V;
@@ -1952,8 +1952,10 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
     require(in.type == CFX_CELL || in.type == CFX_INTERIOR_FACET, CFX_ERR_INVALID_ARGUMENT,
             "cfx_form_create: integral type must be cell or interior_facet");
     const bool user = user_integrand_known(in.kernel);
-    const bool bilinear = user ? user_integrand_rank(in.kernel) == 2 : in.kernel < 100;
-    require(bilinear == (rank == 2), CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: kernel rank does not match the form");
+    // built-in ids: below 100 bilinear (CFX_K_*), 100..199 linear (CFX_L_*), 200..299 functionals (CFX_M_*)
+    const int kernel_rank = user ? user_integrand_rank(in.kernel) : (in.kernel < 100 ? 2 : (in.kernel < 200 ? 1 : 0));
+    const bool bilinear = kernel_rank == 2;
+    require(kernel_rank == rank, CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: kernel rank does not match the form");
     require(in.qdegree >= 0 && in.qdegree <= CFX_QUAD_MAX_DEGREE, CFX_ERR_INVALID_ARGUMENT,
             "cfx_form_create: quadrature degree out of range");
     if (user)
@@ -1981,6 +1983,10 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
                 "cfx_form_create: runtime rules of an interior-facet integral are facet-hosted rules over interior rows "
                 "(cfx_cut_create_facets with row_width 4)");
     }
+    else if (in.type == CFX_INTERIOR_FACET && rank == 0)
+      throw Error(CFX_ERR_INVALID_ARGUMENT,
+                  "cfx_form_create: interior-facet integrals of a functional take registered facet integrands "
+                  "(cfx_integrand_register_variant with rank 0, facet 1)");
     else if (in.type == CFX_INTERIOR_FACET)
     {
       require(in.kernel == CFX_K_GHOST_GRADJUMP || in.kernel == CFX_K_EXTENSION_L2 || in.kernel == CFX_K_JUMP
@@ -2002,6 +2008,12 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
       require(in.type == CFX_CELL && V->degree <= 2 && V1->degree <= 2 && user_integrand_kind(in.kernel) == 0,
               CFX_ERR_INVALID_ARGUMENT,
               "cfx_form_create: a cell integral takes an integrand registered with cfx_integrand_register (spaces of degree 1 or 2)");
+    else if (rank == 0)
+      require((in.kernel == CFX_M_FIELD || in.kernel == CFX_M_L2_DIFF || in.kernel == CFX_M_H1_SEMI)
+                  && (V->degree == 1 || V->degree == 2) && V->bs >= 1 && V->bs <= 3,
+              CFX_ERR_INVALID_ARGUMENT,
+              "cfx_form_create: unknown functional id (CFX_M_FIELD, CFX_M_L2_DIFF, CFX_M_H1_SEMI on Lagrange spaces of degree "
+              "1 or 2, block size 1..3)");
     else
       require(in.kernel == CFX_K_MASS || in.kernel == CFX_K_STIFFNESS || in.kernel == CFX_K_NITSCHE
                   || in.kernel == CFX_K_ELASTICITY || in.kernel == CFX_L_SOURCE || in.kernel == CFX_L_NITSCHE_RHS
@@ -2056,6 +2068,29 @@ static int form_create_impl(cfx_space_t V, cfx_space_t V1, int rank, int n_integ
                   || in.kernel == CFX_K_ELASTICITY || (rect && user),
               CFX_ERR_INVALID_ARGUMENT, "cfx_form_create: a coefficient is accepted by the mass, stiffness and elasticity terms");
       if (in.coefficient) I.coefficient = to_device(in.coefficient, V->ndofs);
+    }
+    else if (rank == 0)
+    {
+      // `coefficient` = u_h, a Function of the form's space.  A registered integrand may or may not read one (interior
+      // facets pack it [2][ND]: scalar); the built-ins say which they need
+      const int field = (int)in.params[0];
+      if (user)
+        require(in.type == CFX_CELL || in.coefficient == nullptr || V->bs == 1, CFX_ERR_INVALID_ARGUMENT,
+                "cfx_form_create: the single `coefficient` of an interior-facet integrand is scalar (a vector-valued Function "
+                "goes into a coefficient list)");
+      else
+      {
+        const bool analytic = field == CFX_F_ONE || field == CFX_F_SINPROD || field == CFX_F_POISSON_RHS;
+        const bool wants = in.kernel != CFX_M_FIELD || field == CFX_F_COEFFICIENT;
+        require(in.kernel != CFX_M_FIELD || analytic || (field == CFX_F_COEFFICIENT && V->bs == 1), CFX_ERR_INVALID_ARGUMENT,
+                "CFX_M_FIELD: params[0] is an analytic field id, or CFX_F_COEFFICIENT on a scalar space (bs = 1)");
+        require(in.kernel != CFX_M_L2_DIFF || in.params[2] == 0.0 || (analytic && V->bs == 1), CFX_ERR_INVALID_ARGUMENT,
+                "CFX_M_L2_DIFF: with params[2] != 0 the space is scalar (bs = 1) and params[0] an analytic field id");
+        require(wants == (in.coefficient != nullptr), CFX_ERR_INVALID_ARGUMENT,
+                "cfx_form_create: a functional of u_h takes its dof values in `coefficient` (CFX_M_FIELD: with the field id "
+                "CFX_F_COEFFICIENT and only with it)");
+      }
+      if (in.coefficient) I.coefficient = to_device(in.coefficient, V->ndofs * V->bs);
     }
     else
     {
@@ -2114,6 +2149,7 @@ int cfx_form_prepare(cfx_form_t a)
   CFX_API_BEGIN
   require(a != nullptr, CFX_ERR_INVALID_ARGUMENT, "cfx_form_prepare: null argument");
   validate_form(a);
+  if (a->rank == 0) return CFX_OK; // a functional has no rows: nothing to build
   if (!force_atomic() && !a->rectangular()) prepare_form_tables(a);
   CFX_API_END
 }
@@ -2642,8 +2678,14 @@ int cfx_tabulate_entity(cfx_form_t a, int integral, int64_t index, int use_rule,
   require(index >= 0 && index < limit, CFX_ERR_OUT_OF_RANGE, "entity index out of range");
   const int nloc = V->ndofs_cell * V->bs * (I.type == CFX_INTERIOR_FACET ? 2 : 1);
   const int nloc1 = a->rectangular() ? a->V1->ndofs_cell * a->V1->bs * (I.type == CFX_INTERIOR_FACET ? 2 : 1) : nloc;
-  const int64_t n = a->rank == 2 ? (int64_t)nloc * nloc1 : nloc;
+  const int64_t n = a->rank == 2 ? (int64_t)nloc * nloc1 : (a->rank == 1 ? nloc : 1);
   OutArray<double> out(Ae, n, false);
+  if (a->rank == 0)
+  {
+    functional_entity(a, I, index, use_rule, out.dev);
+    out.finish();
+    return CFX_OK;
+  }
   ZeroFlag err;
   AsmArgs A{};
   A.x = V->mesh->x.p; A.conn = V->mesh->conn.p; A.dofmap = V->dofmap.p;

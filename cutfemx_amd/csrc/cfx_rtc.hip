@@ -595,13 +595,57 @@ std::string coefficient_pack_source(const Variant& v)
   return s + "}\n";
 }
 
-std::string wrapper_source(const UserIntegrand& u, const Variant& v)
+// Rank-0 integrands (functionals): the same stage-1 texts with another ending.  The local tensor is ONE double that the
+// integrand adds to; the block then sums its 256 values -- a wave64 sum by __shfl_down, the four wave sums through LDS,
+// both in a fixed order -- and stores one partial per block at out[blockIdx.x] (the engine's own second kernel adds the
+// partials: cfx_scalar.hip).  The sum has a barrier, so no thread may leave before it: the early `return` of the entity
+// range check becomes a predicate around the body, and a block wholly past the count stores the partial 0.
+const char* kBlockStore = R"RTC(
+__device__ __forceinline__ void cfx_block_store(double v, double* out)
 {
-  if (v.coefs.empty()) return u.kind == 1 ? kFacetWrapper : kWrapper;
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  __shared__ double cfx_wave_sums[4];
+  if ((threadIdx.x & 63) == 0) cfx_wave_sums[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = (cfx_wave_sums[0] + cfx_wave_sums[1]) + (cfx_wave_sums[2] + cfx_wave_sums[3]);
+}
+)RTC";
+
+std::string rank0_text(const UserIntegrand& u)
+{
   std::string w;
   if (u.kind == 1)
   {
-    w = replace_n(kFacetWrapper, "cfx_facet_stage(const RtcFacetArgs& A)", "cfx_facet_stage(const RtcFacetArgs& A, const RtcCoefArgs& CW)", 1);
+    w = replace_n(kFacetWrapper, "  if (f >= n) return;\n", "  double cfx_m = 0.0;\n  if (f < n)\n  {\n", 1);
+    w = replace_n(w, "  double T[4 * CFXW_NR * CFXW_NC];\n  for (int i = 0; i < 4 * CFXW_NR * CFXW_NC; ++i) T[i] = 0.0;\n",
+                  "  double T[1] = {0.0};\n", 1);
+    w = replace_n(w, "  for (int i = 0; i < 4 * CFXW_NR * CFXW_NC; ++i) A.out[f * (4 * CFXW_NR * CFXW_NC) + i] = T[i];\n}\n",
+                  "  cfx_m = T[0];\n  }\n  cfx_block_store(cfx_m, A.out);\n}\n", 1);
+  }
+  else
+  {
+    w = replace_n(kWrapper, "  if (e >= n) return;\n", "  double cfx_m = 0.0;\n  if (e < n)\n  {\n", 1);
+    w = replace_n(w, "  const int NT = A.rank == 2 ? CFXW_NR * CFXW_NC : CFXW_NR;\n", "", 1);
+    w = replace_n(w, "  double T[CFXW_NR * CFXW_NC];\n  for (int i = 0; i < CFXW_NR * CFXW_NC; ++i) T[i] = 0.0;\n",
+                  "  double T[1] = {0.0};\n", 1);
+    w = replace_n(w,
+                  "  if (A.out_mode == 0)\n    for (int i = 0; i < NT; ++i) A.out[e * NT + i] = T[i];\n  else\n  {\n"
+                  "    const cfx_i64 at = A.out_mode == 2 ? cell : e;\n"
+                  "    for (int i = 0; i < NT; ++i) A.out[(cfx_i64)i * A.out_stride + at] = T[i];\n  }\n}\n",
+                  "  cfx_m = T[0];\n  }\n  cfx_block_store(cfx_m, A.out);\n}\n", 1);
+  }
+  return kBlockStore + w;
+}
+
+std::string wrapper_source(const UserIntegrand& u, const Variant& v)
+{
+  const std::string cell_text = u.rank == 0 && u.kind == 0 ? rank0_text(u) : std::string(kWrapper);
+  const std::string facet_text = u.rank == 0 && u.kind == 1 ? rank0_text(u) : std::string(kFacetWrapper);
+  if (v.coefs.empty()) return u.kind == 1 ? facet_text : cell_text;
+  std::string w;
+  if (u.kind == 1)
+  {
+    w = replace_n(facet_text, "cfx_facet_stage(const RtcFacetArgs& A)", "cfx_facet_stage(const RtcFacetArgs& A, const RtcCoefArgs& CW)", 1);
     w = replace_n(w,
                   "  double w[2 * CFXW_ND];\n  if (A.coeff)\n    for (int s = 0; s < 2; ++s)\n"
                   "      for (int j = 0; j < CFXW_ND; ++j) w[s * CFXW_ND + j] = A.coeff[A.dofmap[(s ? c1 : c0) * CFXW_ND + j]];\n",
@@ -613,7 +657,7 @@ std::string wrapper_source(const UserIntegrand& u, const Variant& v)
   }
   else
   {
-    w = replace_n(kWrapper, "cfx_user_stage1(RtcArgs A)", "cfx_user_stage1(RtcArgs A, RtcCoefArgs CW)", 1);
+    w = replace_n(cell_text, "cfx_user_stage1(RtcArgs A)", "cfx_user_stage1(RtcArgs A, RtcCoefArgs CW)", 1);
     w = replace_n(w,
                   "  double w[CFXW_NR];\n  if (A.coeff)\n    for (int j = 0; j < CFXW_ND; ++j)\n"
                   "      for (int b = 0; b < A.coeff_bs; ++b) w[j * A.coeff_bs + b] = A.coeff[(cfx_i64)A.dofmap[cell * CFXW_ND + j] * "
@@ -795,8 +839,8 @@ void user_coefficients_check(const cfx_form_s* a, const cfx_integral_dev& I)
 // stage 1 of a user integrand over the standard entities (runtime = false) or the runtime rules of integral I of form a:
 // local tensors into `out` (out_mode / out_stride: see RtcArgs); `first` / `count` >= 0 restrict the launch to one entity.
 // A form between two spaces stages [NDB0][NDB1] tensors (rows: test space, columns: trial space).
-void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, double* out, int out_mode, int64_t out_stride,
-                 int64_t only_index)
+int64_t user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, double* out, int out_mode, int64_t out_stride,
+                    int64_t only_index)
 {
   std::lock_guard<std::mutex> lock(rtc_mutex());
   const cfx_space_s* V = a->V;
@@ -805,6 +849,7 @@ void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, d
           CFX_ERR_INVALID_ARGUMENT, "user integrands serve cell integrals of Lagrange spaces of degree 1 or 2");
   UserIntegrand& u = integrands()[I.kernel - CFX_K_USER_BASE];
   require(u.kind == 0, CFX_ERR_INVALID_ARGUMENT, "this user integrand was registered for interior-facet integrals");
+  require(u.rank == a->rank, CFX_ERR_INVALID_ARGUMENT, "user integrand: the integrand's rank does not match the form");
   const Variant var = form_variant(a, u, I);
   check_list_variant(u, var);
   RtcCoefArgs CW = coefficient_args(I);
@@ -816,7 +861,7 @@ void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, d
   A.rank = a->rank; A.runtime = runtime ? 1 : 0;
   for (int k = 0; k < 8; ++k) A.params[k] = I.params[k];
   A.coeff = I.coefficient.n > 0 && var.coefs.empty() ? I.coefficient.p : nullptr; // (a list replaces `coefficient`)
-  A.coeff_bs = a->rank == 1 ? V->bs : 1; // (as the built-in kernels pack it: cfx_fem.hip, assemble_cells_kernel)
+  A.coeff_bs = a->rank != 2 ? V->bs : 1; // (as the built-in kernels pack it: cfx_fem.hip, assemble_cells_kernel)
   A.out = out; A.out_mode = out_mode; A.out_stride = out_stride;
   DevN n;
   if (runtime)
@@ -838,14 +883,15 @@ void user_stage1(const cfx_form_s* a, const cfx_integral_dev& I, bool runtime, d
     n = only_index >= 0 ? DevN(1) : I.n_entities.devn();
   }
   A.n_cap = n.cap; A.n_dev = n.dev;
-  if (n.cap == 0) return;
+  if (n.cap == 0) return 0;
   module_launch(function_of(u, var), n.cap, &A, cw);
+  return (n.cap + 255) / 256;
 }
 
 // stage 1 of a user interior-facet integrand over the (c0, lf0, c1, lf1) rows of integral I: macro tensors
 // [facet][2 NDB0][2 NDB1] into `out` (the layout the row gather and the scatters read); only_index >= 0: one facet.
 // Entities past the standard facets integrate over the integral's facet-hosted rules.
-void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* out, int64_t only_index)
+int64_t user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* out, int64_t only_index)
 {
   std::lock_guard<std::mutex> lock(rtc_mutex());
   const cfx_space_s* V = a->V;
@@ -854,8 +900,9 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
   UserIntegrand& u = integrands()[I.kernel - CFX_K_USER_BASE];
   require(u.kind == 1 && I.type == CFX_INTERIOR_FACET, CFX_ERR_INVALID_ARGUMENT,
           "this user integrand was registered for cell integrals (cfx_integrand_register_facet registers facet integrands)");
-  require((V->degree == 1 || V->degree == 2) && (V1->degree == 1 || V1->degree == 2) && a->rank == 2, CFX_ERR_INVALID_ARGUMENT,
-          "user facet integrands serve bilinear forms on Lagrange spaces of degree 1 or 2");
+  require((V->degree == 1 || V->degree == 2) && (V1->degree == 1 || V1->degree == 2) && (a->rank == 2 || a->rank == 0)
+              && u.rank == a->rank,
+          CFX_ERR_INVALID_ARGUMENT, "user facet integrands serve bilinear forms and functionals on Lagrange spaces of degree 1 or 2");
   const Variant var = form_variant(a, u, I);
   check_list_variant(u, var);
   RtcCoefArgs CW = coefficient_args(I);
@@ -880,7 +927,7 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
     const DevN n = only_index >= 0 ? DevN(1) : I.n_entities.devn();
     A.n_cap = n.cap; A.n_dev = n.dev;
     if (n.cap > 0) module_launch(fn_std, n.cap, &A, cw);
-    return;
+    return (n.cap + 255) / 256;
   }
   // [standard facets, facet-hosted rules] (exact lengths: form creation refuses a pending list next to the rules); the
   // rules' entry point gets the pulled-back points of every rule point in two [points][TDIM] arrays indexed by the rules'
@@ -888,6 +935,7 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
   const int64_t lo = only_index >= 0 ? only_index : 0, hi = only_index >= 0 ? only_index + 1 : I.n_entities.value();
   const int64_t mid = std::min(std::max(I.n_std, lo), hi);
   const int64_t nt = 4 * (int64_t)V->ndofs_cell * V->bs * V1->ndofs_cell * V1->bs;
+  const int64_t std_blocks = (mid - lo + 255) / 256; // (a functional: one partial per block, the rules' after the facets')
   A.n_std = I.n_std;
   if (mid > lo)
   {
@@ -902,10 +950,11 @@ void user_stage1_facets(const cfx_form_s* a, const cfx_integral_dev& I, double* 
     A.offsets = I.rules->offsets.p; A.rpoints = I.rules->points.p; A.rweights = I.rules->weights.p;
     A.host_verts = I.rules->host_verts.p;
     A.scratch = scratch.p; A.scratch_stride = nq * var.tdim;
-    A.rows = I.entities.p + 4 * mid; A.out = out + (mid - lo) * nt; A.f0 = mid;
+    A.rows = I.entities.p + 4 * mid; A.out = a->rank == 0 ? out + std_blocks : out + (mid - lo) * nt; A.f0 = mid;
     A.n_cap = hi - mid; A.n_dev = nullptr;
     module_launch(function_of(u, var, true), A.n_cap, &A, cw);
   }
+  return std_blocks + (hi - mid + 255) / 256;
 }
 } // namespace cfx
 
@@ -917,8 +966,9 @@ static int register_integrand(const char* name, const char* source, int rank, in
   CFX_API_BEGIN
   const char* fn = nd1 > 0 ? "cfx_integrand_register2" : "cfx_integrand_register";
   require(name && source && kernel_id, CFX_ERR_INVALID_ARGUMENT, (std::string(fn) + ": null argument").c_str());
-  require(rank == 1 || rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_register: rank must be 1 or 2");
-  require(kind == 0 || rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_register_facet: interior-facet integrands are bilinear");
+  require(rank == 0 || rank == 1 || rank == 2, CFX_ERR_INVALID_ARGUMENT, "cfx_integrand_register: rank must be 0, 1 or 2");
+  require(kind == 0 || rank != 1, CFX_ERR_INVALID_ARGUMENT,
+          "cfx_integrand_register_facet: interior-facet integrands are bilinear (or functionals: rank 0)");
   for (const char* p = name; *p; ++p)
     require((*p >= 'a' && *p <= 'z') || (*p >= 'A' && *p <= 'Z') || *p == '_' || (p != name && *p >= '0' && *p <= '9'),
             CFX_ERR_INVALID_ARGUMENT, (std::string(fn) + ": the name must be a C identifier").c_str());

@@ -42,6 +42,7 @@ EXTENSION_L2 = _lib.K_EXTENSION_L2
 JUMP = _lib.K_JUMP
 SIP = _lib.K_SIP
 SOURCE, NITSCHE_RHS = _lib.L_SOURCE, _lib.L_NITSCHE_RHS
+M_FIELD, M_L2_DIFF, M_H1_SEMI = _lib.M_FIELD, _lib.M_L2_DIFF, _lib.M_H1_SEMI   # functionals (rank 0, assemble_scalar)
 DIV_TEST, DIV_TRIAL = _lib.K_DIV_TEST, _lib.K_DIV_TRIAL   # rectangular blocks: scale div(v) p / scale q div(u)
 F_ONE, F_SINPROD, F_POISSON_RHS, F_COEFFICIENT = _lib.F_ONE, _lib.F_SINPROD, _lib.F_POISSON_RHS, _lib.F_COEFFICIENT
 
@@ -84,8 +85,8 @@ class Integral:
             self._keep_im = keep       # ... and so does what the form of the imaginary parts aliases
         itype = _lib.CELL
         ent_ptr, n_ent = None, 0
-        if self.facets is None and self.rules is not None and self.rules.host_width == 4 and self.kernel in (
-                _lib.K_GHOST_GRADJUMP, _lib.K_JUMP, _lib.K_SIP):
+        if self.facets is None and self.rules is not None and self.rules.host_width == 4 and (
+                self.kernel in (_lib.K_GHOST_GRADJUMP, _lib.K_JUMP, _lib.K_SIP) or self.kernel in _user_integrand_facet):
             itype = _lib.INTERIOR_FACET       # dS over runtime rules only
         if self.facets is not None:
             itype = _lib.INTERIOR_FACET
@@ -293,6 +294,7 @@ class overlap:
 
 _user_integrand_rank: dict[int, int] = {}
 _user_integrand_two: set[int] = set()   # ids of cfx_integrand_register2
+_user_integrand_facet: set[int] = set()  # ids of rank-0 interior-facet integrands (dS over facet-hosted rules alone)
 
 
 def _coefficient_signature(coefficients):
@@ -333,7 +335,9 @@ def register_integrand(name: str, source: str, rank: int = 2, facet: bool = Fals
                              const double* weights)
 
     over (c0, lf0, c1, lf1) rows -- macro tensor [[00, 01], [10, 11]], both cells' coordinate_dofs, {lf0, lf1}
-    (assemble_matrix_impl.h:528-542).  `variant=(tdim, dofs per cell[, bs])`: the variant the source is validated
+    (assemble_matrix_impl.h:528-542).  `rank=0`: the integrand of a functional (assemble_scalar) -- the same argument
+    lists, `A` is `double A[1]`, zero on entry, and the integrand adds its entity's value; with `facet=True` a rank-0
+    interior-facet integrand.  `variant=(tdim, dofs per cell[, bs])`: the variant the source is validated
     against at registration (default (3, 4, 1)).
 
     A bilinear integrand between two spaces (the off-diagonal blocks of `MixedSpace`, forms with a `trial_space`):
@@ -380,6 +384,10 @@ def register_integrand(name: str, source: str, rank: int = 2, facet: bool = Fals
         _user_integrand_rank[kid.value] = 2
         _user_integrand_two.add(kid.value)
         return kid.value
+    if rank not in (0, 1, 2):
+        raise ValueError("register_integrand: rank must be 0, 1 or 2")
+    if variant is None and facet and rank == 0:
+        variant = (3, 4, 1)   # (cfx_integrand_register_facet itself stays bilinear)
     if variant is None and not facet:
         _lib.check(_lib.load().cfx_integrand_register(name.encode(), source.encode(), int(rank), C.byref(kid)))
     elif variant is None:
@@ -389,6 +397,8 @@ def register_integrand(name: str, source: str, rank: int = 2, facet: bool = Fals
         _lib.check(_lib.load().cfx_integrand_register_variant(name.encode(), source.encode(), int(rank), int(bool(facet)),
                                                               int(tdim), int(nd), int(bs), C.byref(kid)))
     _user_integrand_rank[kid.value] = int(rank)
+    if facet and rank == 0:
+        _user_integrand_facet.add(kid.value)
     return kid.value
 
 
@@ -420,8 +430,9 @@ def form(integrals, V: FunctionSpace, rank: int | None = None, trial_space: Func
     with `trial_space`."""
     integrals = list(integrals)
     if rank is None:
-        ranks = {_user_integrand_rank[i.kernel] if i.kernel in _user_integrand_rank else (2 if i.kernel < 100 else 1)
-                 for i in integrals}
+        # built-in ids: below 100 bilinear, 100..199 linear, 200..299 functionals
+        ranks = {_user_integrand_rank[i.kernel] if i.kernel in _user_integrand_rank
+                 else (2 if i.kernel < 100 else 1 if i.kernel < 200 else 0) for i in integrals}
         if len(ranks) != 1:
             raise ValueError("all integrals of a form must have the same rank")
         rank = ranks.pop()
@@ -679,13 +690,32 @@ def set_bc(b, bc_markers, bc_values, x0=None, alpha: float = 1.0):
     return b
 
 
-def assemble_scalar(M: CutForm) -> float:
-    """Functional int f over the form's cells and runtime rules (python/cutfemx/fem.py:522-528).
-    `M` is a linear form of SOURCE integrals: the Lagrange basis is a partition of unity, so the
-    functional is the sum of the assembled vector (python/tests/test_cut_api.py:796-811 checks the
-    reference the same way)."""
+def assemble_scalar(M: CutForm, out=None):
+    """The functional of a form (python/cutfemx/fem.py:522-528 -> assemble_scalar_impl.h:26-275).
+
+    A rank-0 form (M_FIELD / M_L2_DIFF / M_H1_SEMI or registered rank-0 integrands) is assembled in HBM
+    (cfx_assemble_scalar) and returned as a float.  `out`: a one-element float64 device torch tensor that is overwritten
+    with the value and returned instead -- no host read-back, also inside a cutfemx_amd.step.
+
+    A linear form of SOURCE integrals keeps its older route: the Lagrange basis is a partition of unity, so the
+    functional int f is the sum of the assembled vector (python/tests/test_cut_api.py:796-811 checks the reference the
+    same way)."""
+    if M.rank == 0 and not _is_complex(M.dtype):
+        if out is not None:
+            import torch
+            if not (_lib.is_torch(out) and out.is_cuda and out.dtype == torch.float64 and out.numel() == 1
+                    and out.is_contiguous()):
+                raise TypeError("assemble_scalar: `out` is a one-element float64 device torch tensor")
+            _lib.check(_lib.lib().cfx_assemble_scalar(M._h, C.c_void_p(out.data_ptr())))
+            return out
+        v = C.c_double()
+        _lib.check(_lib.lib().cfx_assemble_scalar(M._h, C.byref(v)))
+        return float(v.value)
     if M.rank != 1 or any(i.kernel != SOURCE for i in M.integrals):
-        raise ValueError("assemble_scalar takes a linear form made of SOURCE integrals (f dx)")
+        raise ValueError("assemble_scalar takes a rank-0 form (a functional: M_* or registered rank-0 integrands) or a "
+                         "linear form made of SOURCE integrals (f dx)")
+    if out is not None:
+        raise ValueError("assemble_scalar: `out` goes with a rank-0 form")
     b = assemble_vector(M)
     return complex(b.sum()) if _is_complex(M.dtype) else float(b.sum())
 
@@ -966,7 +996,7 @@ def tabulate_entity(a: CutForm, integral: int, index: int, use_rule: bool) -> np
     nloc = V.ndofs_cell * V.bs * (2 if facet_type else 1)
     V1 = getattr(a, "trial_space", V)
     nloc1 = nloc if V1 is V else V1.ndofs_cell * V1.bs * (2 if facet_type else 1)   # [(nd0 bs0) x (nd1 bs1)] row-major for rectangular forms (facets: both cells)
-    Ae = np.zeros((nloc, nloc1) if a.rank == 2 else (nloc,))
+    Ae = np.zeros((nloc, nloc1) if a.rank == 2 else (nloc,) if a.rank == 1 else (1,))   # a functional: the entity's value
     _lib.check(_lib.lib().cfx_tabulate_entity(a._h, integral, C.c_int64(index), int(use_rule),
                                               Ae.ctypes.data_as(C.c_void_p)))
     return Ae

@@ -56,6 +56,14 @@ def build_forms(V, cut_data, *, order: int = 4, gamma: float = 40.0, gamma_g: fl
                          fem.form(a_int, V), fem.form(L_int, V))
 
 
+def l2_error_form(system: PoissonSystem, V, uh, *, qdegree: int = 6):
+    """The squared L2 error of python/demo/demo_poisson.py:213-214, `(uh - u_exact)**2 * dx_omega` with u_exact =
+    prod sin(pi x_i), over [inside cells, volume rules] of `system`: a rank-0 form for fem.assemble_scalar (take the
+    square root of its value).  `uh`: a Function of `V` or its dof values, host or HBM."""
+    return fem.form([fem.Integral(fem.M_L2_DIFF, cells=system.inside_cells, rules=system.volume_rules,
+                                  params=(fem.F_SINPROD, 1.0, 1.0), qdegree=qdegree, coefficient=uh)], V)
+
+
 @dataclass
 class DGPoissonSystem:
     function_space: object

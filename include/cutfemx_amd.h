@@ -94,6 +94,15 @@ extern "C" {
 #define CFX_L_SOURCE 101        /* f v; params[0]=field id, params[1]=scale    */
 #define CFX_L_NITSCHE_RHS 102   /* -dn(v) g + gamma/h g v; params[0]=gamma,
                                    params[1]=field id of g, params[2]=scale    */
+/* functionals (rank 0, cfx_assemble_scalar): cell integrals over standard cells and / or cell-hosted runtime rules
+ * (cfx_facet_rules_to_cells rules included) of a Lagrange space of degree 1 or 2; `coefficient` = the dof values of
+ * u_h, a Function of the form's space (ndofs * bs doubles); params[0] = field id, params[1] = scale (the convention
+ * of CFX_L_SOURCE) */
+#define CFX_M_FIELD 201         /* params[1] f, f = field params[0]: CFX_F_COEFFICIENT gives int u_h (bs = 1), CFX_F_ONE
+                                   the volume / area / perimeter of the measure */
+#define CFX_M_L2_DIFF 202       /* params[1] |u_h - params[2] g|^2, g = the ANALYTIC field params[0]; params[2] != 0 needs
+                                   bs = 1; params[2] = 0: the squared L2 norm summed over the components (bs <= 3) */
+#define CFX_M_H1_SEMI 203       /* params[1] |grad u_h|^2, summed over the components */
 /* analytic fields evaluated at physical quadrature points */
 #define CFX_F_ONE 0             /* 1 */
 #define CFX_F_SINPROD 1         /* prod_i sin(pi x_i) */
@@ -153,7 +162,7 @@ typedef struct
 {
   int32_t type;            /* CFX_CELL | CFX_INTERIOR_FACET (exterior-facet terms are CFX_CELL integrals over
                               cfx_facet_rules_to_cells rules)                                          */
-  int32_t kernel;          /* CFX_K_* (rank 2) or CFX_L_* (rank 1)             */
+  int32_t kernel;          /* CFX_K_* (rank 2), CFX_L_* (rank 1) or CFX_M_* (rank 0) */
   int32_t qdegree;         /* standard quadrature degree for uncut entities    */
   int32_t point_stride;    /* doubles per point in point_data                  */
   const int32_t* entities; /* cells: ids; interior facets: (c0,lf0,c1,lf1)     */
@@ -413,6 +422,10 @@ int cfx_space_destroy(cfx_space_t V);
 
 /* ---- forms: dolfinx_custom_data::fem::Form, Form.h:119-178, built as in
  *      python/cutfemx/wrappers/fem.cpp:124-172 ------------------------------- */
+/* rank 0: a functional M = sum_integrals sum_entities int m (assemble_scalar_impl.h:26-275).  V names the mesh and is
+ * the space of every integral's single `coefficient`; n_integrals = 0 is the functional 0.  Interior-facet integrals
+ * of a functional take registered facet integrands.  Such a form builds no row plan (cfx_form_prepare succeeds and
+ * does nothing); everything that needs rows -- sparsity, matrix / vector assembly, lifting, active domain -- refuses it */
 int cfx_form_create(cfx_space_t V, int rank, int n_integrals,
                     const cfx_integral* integrals, cfx_form_t* out);
 /* Bilinear form with DIFFERENT test and trial spaces on one mesh (Form::function_spaces() = {V_test, V_trial},
@@ -449,6 +462,14 @@ int cfx_assemble_matrix_zeroed(cfx_form_t a, cfx_pattern_t pattern, const int8_t
                                const int8_t* bc1, double* values);
 /* assemble_vector(): assembler.h:252-262 -> assemble_vector_impl.h:573-767 */
 int cfx_assemble_vector(cfx_form_t L, double* b);
+/* assemble_scalar(): cpp/dolfinx_custom_data/fem/assemble_scalar_impl.h:26-275 (python/cutfemx/fem.py assemble_scalar).
+ * OVERWRITES *value with the functional of the rank-0 form M (it does not accumulate).  `value` is a host or a device
+ * pointer: a device pointer leaves the stream running and makes no host round trip (cfx_sync_count does not grow, also
+ * inside cfx_step_begin / cfx_step_end, where a void step leaves 0 and is repeated like any other); a host pointer costs
+ * one read-back.  One thread per entity sums its points in FP64, a block of 256 sums its threads in a fixed order and
+ * stores one partial, a second single-block launch sums the partials in a fixed order: no floating-point atomics, the
+ * same bits for the same inputs.  Several GPUs: each rank passes the entities it owns and the caller sums the ranks. */
+int cfx_assemble_scalar(cfx_form_t M, double* value);
 
 /* Dirichlet lifting  b <- b - alpha A (g - x0)  restricted to the Dirichlet columns, formed entity by
  * entity without the assembled matrix: dolfinx_custom_data::fem::apply_lifting / lift_bc_impl
@@ -487,6 +508,7 @@ int cfx_csr_block_merge(int nbr, int nbc, const int64_t* const* indptr, const in
 int cfx_csr_permute(int64_t nrows, int64_t ncols, const int64_t* indptr, const int32_t* indices, const double* values,
                     const int32_t* row_perm, const int32_t* col_perm, int64_t** out_indptr, int32_t** out_indices,
                     double** out_values);
+/* (a rank-0 form: ONE double, the entity's contribution to the functional) */
 int cfx_tabulate_entity(cfx_form_t a, int integral, int64_t index, int use_rule, double* Ae);
 
 /* ---- user-supplied integrands: the runtime-generated kernel of a form
@@ -512,6 +534,11 @@ int cfx_tabulate_entity(cfx_form_t a, int integral, int64_t index, int use_rule,
  *      row gather -- or the entity-parallel scatter -- then assembles them like those of the built-in integrands that
  *      are not formed in line.  A source that does not compile is CFX_ERR_INVALID_ARGUMENT with the compiler log in
  *      cfx_last_error(); compilation needs no GPU (hipRTC targets gfx950 explicitly), loading the code object does. */
+/* rank 0 (functionals): the same argument lists; A is `double A[1]`, zero on entry, and the integrand ADDS its entity's
+ * value.  The compiled wrapper ends in the block sum of cfx_assemble_scalar instead of staging a local tensor.  `w`
+ * holds the ND x CFX_BS dofs of `coefficient` (a Function of the form's space; interior facets: [2][ND], scalar) or the
+ * coefficient list.  cfx_integrand_register_variant(..., rank 0, facet 1, ...) registers a rank-0 interior-facet
+ * integrand (over standard facets and / or facet-hosted rules); cfx_integrand_register_facet stays bilinear. */
 int cfx_integrand_register(const char* name, const char* source, int rank, int* kernel_id);
 int cfx_integrand_compile(int kernel_id, int tdim, int ndofs_cell); /* compile a (tdim, dofs per cell) variant now */
 /* Vector-valued spaces (bs > 1): CFX_BS = the space's block size and CFX_NDB = CFX_ND * CFX_BS are defined as well;

@@ -482,6 +482,17 @@ inline void assemble_matrix_zeroed(std::span<double> values, const Form& a, cons
 /// assemble_vector(): assembler.h:252-262
 inline void assemble_vector(std::span<double> b, const Form& L) { check(cfx_assemble_vector(L.handle.h, b.data())); }
 
+/// assemble_scalar(): assemble_scalar_impl.h:26-275 -- the value of a rank-0 form (Form::create(V, 0, integrals) with
+/// CFX_M_* or registered rank-0 integrands), summed in HBM in a fixed order; one read-back
+inline double assemble_scalar(const Form& M)
+{
+  double value = 0.0;
+  check(cfx_assemble_scalar(M.handle.h, &value));
+  return value;
+}
+/// ... into one double in HBM: the stream keeps running, no host round trip (also inside a sync-free step)
+inline void assemble_scalar(const Form& M, double* device_value) { check(cfx_assemble_scalar(M.handle.h, device_value)); }
+
 /// complex128 instantiation (T = std::complex<double>, wrappers/fem.cpp:490-500; test_complex_assembly.py:24-95):
 /// `scales` = the complex constant of every integral of the form (empty: all 1); accumulates into `values` / `b`
 inline void assemble_matrix(std::span<std::complex<double>> values, const Form& a, const SparsityPattern& pattern,
