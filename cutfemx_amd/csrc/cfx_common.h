@@ -877,6 +877,7 @@ struct cfx_space_s
   ~cfx_space_s() { cfx::step_forget_owner(this); pcache.drop(); }
   bool lists_short_overflow = false; // a short-list row overflowed the 128-slot set once: hashed rows all go wide
   bool long_rows = false; // a sparsity build of this space overflowed the 63-entry row sets: start with the wide kernel
+  bool huge_rows = false; // ... and the 511-entry sets of the wide kernel too: start with the 2048-slot form
   const cfx::Adjacency& dof_cells()
   {
     // a P1 space whose dofmap aliases the geometry dofmap shares the mesh's vertex->cells table

@@ -2229,8 +2229,9 @@ __global__ void __launch_bounds__(kWave, CFX_PLAIN_WAVES) assemble_rows_plain_ke
     for (int k = 0; k < R; ++k)
     {
       const int t = base + k * G + gl;
-      // the cell id is only the key of its mark byte: not read for rows whose incident cells share one mark
-      cell[k] = t < nc ? (umark ? 0 : A.d2c[cb + t]) : -1;
+      // staged form: the cell id is only the key of its mark byte, not read for rows whose incident cells share one
+      // mark; the unstaged form reads the cell's dof row by it
+      cell[k] = t < nc ? ((STAGE && umark) ? 0 : A.d2c[cb + t]) : -1;
       s4[k] = t < nc ? A.slot4[cb + t] : 0u;
     }
 #pragma unroll
@@ -2670,9 +2671,11 @@ __global__ void __launch_bounds__(kWave, CFX_TILE_WAVES) assemble_tiles_plain_ke
       else
       {
         const double scale = (double)rep[k]; // the same cell in several inline integrals; 0: no item
-        dsum += diag_bc ? 0.0 : dg * scale;
+        // (a lane without an item computed on a dummy cell made of the row's stencil positions: where those vertices are
+        // coplanar -- the base of a cone around its apex -- its numbers are not finite, and 0 * them is no zero)
+        dsum += (diag_bc || !rep[k]) ? 0.0 : dg * scale;
 #pragma unroll
-        for (int q = 0; q < TDIM; ++q) ov[q] *= scale;
+        for (int q = 0; q < TDIM; ++q) ov[q] = rep[k] ? ov[q] * scale : 0.0;
       }
       if (!fast)
       {

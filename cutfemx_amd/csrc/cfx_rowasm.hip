@@ -2637,7 +2637,9 @@ const Stencil& space_stencil(cfx_space_s* V)
     if (need < (free_b + cached_b) / 3 && env_on<Sw::STENCIL_STAGED>()) { staged.alloc(V->ndofs * 64); A.tmp = staged.p; }
   }
   launch("stencil_rows", pattern_rows_kernel<4, 64>, wave_grid((V->ndofs + 15) / 16), dim3(kWave), 0, A);
-  if (read_scalar(overflow.p)) return S; // a vertex with more than 63 neighbours: keep the hashed paths
+  // The 64-slot set keeps one slot free (a full table cannot be told from an overflowing one): a list of 63 entries, the
+  // vertex itself included, is the longest that fits.  A vertex with more than 62 neighbours: keep the hashed paths.
+  if (read_scalar(overflow.p)) return S;
   S.max_len = read_scalar(maxlen.p);
   S.offsets.alloc(V->ndofs + 1);
   exclusive_scan(counts.p, S.offsets.p, V->ndofs);
@@ -3900,6 +3902,7 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
     {
       // a short static list with more than 127 - 40 facet couplings, or a row beyond 511: all rows wide from now on
       V->lists_short_overflow = true;
+      V->long_rows = true; // (the 64-slot attempt below could only overflow again)
       split_hashed = false;
       overflow.zero();
       maxlen.zero();
@@ -3934,8 +3937,19 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
       // other paths hash the list they were given -- n_d rows, exact already)
       if (use_stencil) { S.n_active = DevN(n_h_c.value()); n_d = S.n_active.cap; }
       else S.n_active = DevN(n_d);
-      launch("pattern_rows_wide", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
-      require(!read_scalar(overflow.p), CFX_ERR_RUNTIME, "sparsity: a row couples more than 511 dofs");
+      if (!V->huge_rows) launch("pattern_rows_wide", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
+      if (V->huge_rows || read_scalar(overflow.p))
+      {
+        // a row beyond 511 columns (a vertex of high valence in a degree-2 space, a hub of facet couplings): the same
+        // kernel with a 2048-slot set.  Such a pattern is assembled by the entity-parallel kernels (assemble_matrix_rows
+        // gathers rows of at most 512 columns).  The flag stays with the space: its later patterns start here.
+        V->huge_rows = true;
+        T = 2048;
+        overflow.zero();
+        maxlen.zero();
+        launch("pattern_rows_huge", pattern_rows_kernel<64, 2048>, wave_grid(n_d), dim3(kWave), 0, S);
+        require(!read_scalar(overflow.p), CFX_ERR_RUNTIME, "sparsity: a row couples more than 2047 dofs");
+      }
     }
   }
   if (use_stencil)
@@ -4053,7 +4067,8 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
     else
     {
       S.indptr = P->indptr.p; S.indices = P->indices.p;
-      launch("pattern_rows_wide_write", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
+      if (T == 2048) launch("pattern_rows_huge_write", pattern_rows_kernel<64, 2048>, wave_grid(n_d), dim3(kWave), 0, S);
+      else launch("pattern_rows_wide_write", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
     }
   }
   // full_rows = [dofs with at most 32 neighbours | the others]: the edge dofs of a degree-2 space (7 of 8 dofs, at most

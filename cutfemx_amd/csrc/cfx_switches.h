@@ -21,7 +21,7 @@
   CFX_SWITCH(ASSEMBLY,           string,     call,  "atomic: the entity-parallel FP64-atomic kernels instead of the row gather") \
   CFX_SWITCH(STENCIL,            first_char, build, "0: no mesh-static row stencil (P1): hashed sparsity, searching gather") \
   CFX_SWITCH(STENCIL_LISTS,      first_char, build, "0: no neighbour lists for the other spaces (degree 2, vector-valued, DG)") \
-  CFX_SWITCH(STENCIL_STAGED,     first_char, build, "0: two-pass stencil rows and tiles, the build a card short of memory takes (no test provokes that: the only handle on it)") \
+  CFX_SWITCH(STENCIL_STAGED,     first_char, build, "0: two-pass stencil rows and tiles, the build a card short of memory takes (so does a tile whose union outgrows its staging row; tests reach both through this switch alone)") \
   CFX_SWITCH(TILES,              first_char, build, "0: no row tiles") \
   CFX_SWITCH(LATTICE_ROWS,       first_char, build, "0: no lattice flags and no template: every plain row is computed by the tile kernel") \
   CFX_SWITCH(LATTICE_SOURCE,     first_char, call,  "0: the P1 series source term of the lattice rows hex by hex instead of its closed form per row") \
@@ -39,7 +39,7 @@
   CFX_SWITCH(SOURCE_SERIES,      first_char, call,  "0: the P1 source term by quadrature instead of its series") \
   CFX_SWITCH(SOURCE_GROUPS,      first_char, call,  "0: the P1 series source term cell by cell instead of one hex per lane") \
   CFX_SWITCH(STAGING_NAN,        first_char, call,  "1 (tests): the hex-corner planes of the staging start as NaN") \
-  CFX_SWITCH(PLAIN_STAGE,        first_char, call,  "0: plain rows without LDS staging, the form stencils longer than 32 take (no test has such a mesh: the only handle on it)") \
+  CFX_SWITCH(PLAIN_STAGE,        first_char, call,  "0: plain rows without LDS staging, the form that meshes with stencils longer than 32 take by themselves") \
   CFX_SWITCH(MFMA,               first_char, call,  "0: generic rows instead of the MFMA kernel for staged elasticity tensors") \
   CFX_SWITCH(CUT_TENSORS_P1,     first_char, call,  "0: the generic tensors of cut P1 cells") \
   CFX_SWITCH(RECT_GATHER,        first_char, call,  "0: rectangular blocks by the entity-parallel atomic kernel") \

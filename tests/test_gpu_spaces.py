@@ -10,11 +10,15 @@ pytestmark = pytest.mark.gpu
 RTOL = 1e-12
 
 
-def setup(oracle, tdim, n, degree, bs, kind="sphere"):
+def setup(oracle, tdim, n, degree, bs, kind="sphere", mesh_phi=None):
+    """`mesh_phi`: (oracle mesh, level-set values) instead of the n^tdim box mesh with the `kind` level set."""
     import cutfemx_amd as cfx
     O = oracle
-    om = O.mesh_box(tdim, n)
-    phi = level_set_values(om.x, tdim, kind)
+    if mesh_phi is None:
+        om = O.mesh_box(tdim, n)
+        phi = level_set_values(om.x, tdim, kind)
+    else:
+        om, phi = mesh_phi
     dofmap, ndofs = cfx.lagrange_dofmap(tdim, om.conn, om.nnodes, degree)
     oV = O.Space(dofmap, ndofs, degree, bs)
     mesh = cfx.Mesh.from_arrays(tdim, om.x, om.conn)
