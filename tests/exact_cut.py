@@ -1,5 +1,6 @@
 """Exact rational reference for P1 cuts of simplices: moments of {phi_h < 0}, {phi_h > 0} and {phi_h = 0} inside a
-simplex, for one or several level sets and for facet hosts, and the local tensors that follow from the moments.
+simplex, for one or several level sets and for facet hosts, and the local tensors that follow from the moments: square
+and rectangular cell tensors, coefficient-weighted ones, coefficient sources, facet and interface terms, lifting.
 
 For a P1 level set the cut part of a simplex is a convex polytope whose vertices are rational functions of the float64
 inputs, and every built-in integrand is a polynomial in the barycentric coordinates, so `fractions.Fraction` gives
@@ -257,15 +258,16 @@ def _ld(q):
 
 
 class Moments:
-    """Moments of one region in all barycentric monomials up to degree 4, normalised by the parent's measure."""
+    """Moments of one region in all barycentric monomials up to `degree` (4: every unweighted built-in; 6: P2 mass
+    times a P2 coefficient), normalised by the parent's measure."""
 
-    def __init__(self, d, clauses=None):
-        self.d = d
-        self.alphas = monomials(d + 1, 4)
+    def __init__(self, d, clauses=None, degree=4):
+        self.d, self.degree = d, degree
+        self.alphas = monomials(d + 1, degree)
         if clauses is None:
             vals = [whole_moment(d, a) for a in self.alphas]
         else:
-            vals = region_moments(d, clauses, self.alphas, 4)
+            vals = region_moments(d, clauses, self.alphas, degree)
         self.m = {a: _ld(v) for a, v in zip(self.alphas, vals)}
 
     def table(self, A, B):
@@ -348,6 +350,80 @@ def source_one(mom, xc, degree, scale=1.0):
     _, vol = cell_geometry(xc)
     one = [tuple([0] * (mom.d + 1))]
     return (LD(scale) * vol * (C @ mom.table(A, one))[:, 0]).astype(np.float64)
+
+
+# ---- two spaces, coefficient weights, coefficient sources -----------------------------------------------------------
+def _diag_blocks(T, bs):
+    """The scalar tensor on the diagonal of the bs x bs component blocks: (dof i, component a) at i * bs + a."""
+    return T if bs == 1 else np.kron(T, np.eye(bs, dtype=T.dtype))
+
+
+def rect_tensor(kind, mom, xc, deg0, bs0, deg1, bs1, params=()):
+    """Cell tensor between a test space (degree deg0, block size bs0) and a trial space (deg1, bs1) over the region
+    of `mom`: [(nd0 bs0) x (nd1 bs1)] row-major, dof-major, component-minor (include/cutfemx_amd.h).
+    'mass': C0 M C1^T and 'stiffness' (bs0 == bs1, the scalar block on the component diagonal);
+    'div_test': scale d_a N0_i N1_j at row i * tdim + a (bs0 = tdim, bs1 = 1);
+    'div_trial': scale N0_i d_b N1_j at column j * tdim + b (bs0 = 1, bs1 = tdim); params = (scale,)."""
+    d = mom.d
+    A0, C0, B0, D0 = basis(d, deg0)
+    A1, C1, B1, D1 = basis(d, deg1)
+    G, vol = cell_geometry(xc)
+    if kind in ("mass", "stiffness"):
+        if bs0 != bs1:
+            raise ValueError("mass and stiffness blocks need bs0 == bs1")
+        if kind == "mass":
+            T = vol * (C0 @ mom.table(A0, A1) @ C1.T)
+        else:
+            W = np.einsum("imp,pq,jnq->imjn", D0, mom.table(B0, B1), D1)            # the order of `grad_moments`
+            T = np.einsum("iaja->ij", vol * np.einsum("imjn,ma,nb->iajb", W, G, G))
+        return _diag_blocks(T, bs0).astype(np.float64)
+    scale = LD(params[0]) if len(params) else LD(1)
+    if kind == "div_test":
+        if (bs0, bs1) != (d, 1):
+            raise ValueError("div_test: vector test space, scalar trial space")
+        T = scale * vol * np.einsum("imp,ma,pq,jq->iaj", D0, G, mom.table(B0, A1), C1)
+        return T.reshape(D0.shape[0] * d, C1.shape[0]).astype(np.float64)
+    if kind == "div_trial":
+        if (bs0, bs1) != (1, d):
+            raise ValueError("div_trial: scalar test space, vector trial space")
+        T = scale * vol * np.einsum("ip,pq,jnq,nb->ijb", C0, mom.table(A0, B1), D1, G)
+        return T.reshape(C0.shape[0], D1.shape[0] * d).astype(np.float64)
+    raise ValueError(kind)
+
+
+def weighted_moments(mom, degree, kappa_cell):
+    """The moments of `mom` against kappa = sum_k N_k kappa_cell[k] (N the basis of `degree`): kappa is expanded in the
+    barycentric monomials like every other factor, so m'(alpha) = sum_r k_r m(alpha + A[r]) for every alpha that
+    leaves room for kappa's degree."""
+    A, C, _, _ = basis(mom.d, degree)
+    k = np.asarray(kappa_cell, dtype=LD) @ C
+    if k.shape != (len(A),):
+        raise ValueError("kappa_cell: one value per dof of the cell")
+    room = mom.degree - degree
+    if room < 0:
+        raise ValueError("moments of too low a degree")
+    out = {}
+    for al in monomials(mom.d + 1, room):
+        out[al] = sum((k[r] * mom.m[tuple(x + y for x, y in zip(al, a))] for r, a in enumerate(A) if k[r] != 0), LD(0))
+    t = Table(out)
+    t.d, t.degree = mom.d, room
+    return t
+
+
+def weighted(kind, mom, xc, degree, kappa_cell, params=()):
+    """'mass', 'stiffness' or 'elasticity' with the integrand multiplied by kappa = sum_k N_k kappa_cell[k], kappa in the
+    form's own (scalar) element.  `mom` needs degree 3 `degree` (mass) or 3 `degree` - 2."""
+    return tensor(kind, weighted_moments(mom, degree, kappa_cell), xc, degree, params)
+
+
+def source_coeff(mom, xc, degree, w_cell, bs=1, scale=1.0):
+    """int f . v with f = sum_j N_j w_cell[j, :]: entry (i, a) at i * bs + a is scale * sum_j M_ij w[j, a], M the exact
+    scalar mass tensor."""
+    A, C, _, _ = basis(mom.d, degree)
+    _, vol = cell_geometry(xc)
+    M = vol * (C @ mom.table(A, A) @ C.T)
+    w = np.asarray(w_cell, dtype=LD).reshape(C.shape[0], bs)
+    return (LD(scale) * (M @ w)).reshape(-1).astype(np.float64)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -540,11 +616,12 @@ def host_case(O, name, which):
     return cached(("hosts", name, which), run)
 
 
-def cut_moments(key, cs, c, selector="phi<0"):
-    """Moments (all barycentric monomials up to degree 4) of the selector's part of cell c, cached."""
+def cut_moments(key, cs, c, selector="phi<0", degree=4):
+    """Moments (all barycentric monomials up to `degree`) of the selector's part of cell c, cached by the degree too."""
     phis = cs.get("phis", [cs["phi"]])
     ph = cell_phi(phis, cs["conn"][c])
-    return cached(("mom", key, selector, int(c)), lambda: Moments(cs["tdim"], [(ph[k], s) for k, s in parse(selector)]))
+    tag = ("mom", key, selector, int(c)) + (() if degree == 4 else (degree,))
+    return cached(tag, lambda: Moments(cs["tdim"], [(ph[k], s) for k, s in parse(selector)], degree))
 
 
 def tensor(kind, mom, xc, degree, params=()):
@@ -594,30 +671,70 @@ def f32_case(O, name):
     return cached(("f32", name), run)
 
 
-def exact_entries(key, cs, dofmap, bs, kind, degree, params=(), inside=None):
-    """COO entries (rows, cols, values) -- or (rows, values) for kind 'source' -- of the form whose entities are the
-    phi<0 rules of every cut cell and, if given, the uncut cells `inside`: exact local tensors scattered with the
-    blocked dofmap (dof i, component a at i * bs + a)."""
+def exact_entries(key, cs, dofmap, bs, kind, degree, params=(), inside=None, trial=None, coefficient=None, mom_degree=4):
+    """COO entries (rows, cols, values) -- or (rows, values) for the kinds 'source' and 'source_coeff' -- of the form
+    whose entities are the phi<0 rules of every kept cut cell and, if given, the uncut cells `inside`: exact local
+    tensors scattered with the blocked dofmap (dof i, component a at i * bs + a).
+    trial = (dofmap1, bs1, degree1): a rectangular block (`rect_tensor`), rows by `dofmap` / `bs`, columns by the trial
+    space's.  coefficient: the dof values of a Function of the form's space -- kappa (one value per dof) for 'mass',
+    'stiffness' and 'elasticity' (`weighted`), the field (bs values per dof) for 'source_coeff' (params = (scale,)).
+    mom_degree: the degree of the moments taken (the integrand's, if above 4)."""
     tdim = cs["tdim"]
-    whole = Moments(tdim)
+    co = None if coefficient is None else np.ascontiguousarray(coefficient, dtype=np.float64)
+
+    def local(c, mom):
+        xc = cs["x"][cs["conn"][c], :tdim]
+        if trial is not None:
+            return rect_tensor(kind, mom, xc, degree, bs, trial[2], trial[1], params)
+        if kind == "source_coeff":
+            return source_coeff(mom, xc, degree, co.reshape(-1, bs)[np.asarray(dofmap[c], dtype=np.int64)], bs, *params)
+        if co is not None:
+            T = weighted(kind, mom, xc, degree, co[np.asarray(dofmap[c], dtype=np.int64)], params)
+        else:
+            T = tensor(kind, mom, xc, degree, params)
+        return _diag_blocks(T, bs) if kind in ("mass", "stiffness") else T
 
     def run():
+        whole = Moments(tdim, degree=mom_degree)
         R, Cc, Vv = [], [], []
-        cells = [(c, cut_moments(key, cs, c)) for c in cs["cut"][cs["keep"]]]
+        cells = [(c, cut_moments(key, cs, c, degree=mom_degree)) for c in cs["cut"][cs["keep"]]]
         cells += [(c, whole) for c in ([] if inside is None else inside)]
         for c, mom in cells:
-            T = tensor(kind, mom, cs["x"][cs["conn"][c], :tdim], degree, params)
-            dofs = (np.asarray(dofmap[c], dtype=np.int64)[:, None] * bs + np.arange(bs)[None, :]).ravel()
+            T = local(c, mom)
+            dofs = _blocked(dofmap[c], bs)
             if T.ndim == 1:
-                if bs != 1:
+                if T.size != dofs.size:
                     raise ValueError("scalar source only")
                 R.append(dofs); Vv.append(T)
             else:
-                R.append(np.repeat(dofs, dofs.size)); Cc.append(np.tile(dofs, dofs.size)); Vv.append(T.ravel())
+                cols = dofs if trial is None else _blocked(trial[0][c], trial[1])
+                R.append(np.repeat(dofs, cols.size)); Cc.append(np.tile(cols, dofs.size)); Vv.append(T.ravel())
         out = (np.concatenate(R), np.concatenate(Cc), np.concatenate(Vv)) if Cc else (np.concatenate(R), np.concatenate(Vv))
         return out
-    return cached(("entries", key, kind, degree, bs, tuple(params), inside is not None,
-                   np.ascontiguousarray(dofmap, dtype=np.int64).tobytes()), run)
+    tag = ("entries", key, kind, degree, bs, tuple(params), inside is not None,
+           np.ascontiguousarray(dofmap, dtype=np.int64).tobytes())
+    if trial is not None or co is not None or mom_degree != 4:
+        tag += (None if trial is None else (np.ascontiguousarray(trial[0], dtype=np.int64).tobytes(), trial[1], trial[2]),
+                None if co is None else co.tobytes(), mom_degree)
+    if inside is not None:
+        tag += (np.ascontiguousarray(inside, dtype=np.int64).tobytes(),)
+    return cached(tag, run)
+
+
+def exact_lift(entries, shape, markers1, g, x0, alpha, b0):
+    """b0 - A_exact @ where(marked, alpha (g - x0), 0) for A_exact given as COO `entries` of `shape`, accumulated in
+    longdouble and rounded once; and the scale of the comparison, max(abs(b0) + abs(A_exact) @ abs(alpha (g - x0)))."""
+    r, c, v = entries
+    g = np.asarray(g, dtype=LD)
+    y = LD(alpha) * (g - (0 if x0 is None else np.asarray(x0, dtype=LD)))
+    y = np.where(np.asarray(markers1) != 0, y, LD(0))
+    if y.shape != (shape[1],) or np.shape(b0) != (shape[0],):
+        raise ValueError("lifting takes trial-space data and a test-space vector")
+    out, mag = np.asarray(b0, dtype=LD).copy(), np.abs(np.asarray(b0, dtype=LD))
+    t = np.asarray(v, dtype=LD) * y[c]
+    np.subtract.at(out, r, t)
+    np.add.at(mag, r, np.abs(t))
+    return out.astype(np.float64), float(mag.max())
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -746,6 +863,23 @@ def facet_tensor(kind, fb, mom, params, bs=1):
     return T if bs == 1 else np.kron(T, np.eye(bs, dtype=LD))
 
 
+def facet_tensor2(kind, fb0, fb1, mom, params):
+    """Local tensor of an interior-facet term between two scalar spaces on one facet row: rows from the test basis
+    `fb0`, columns from the trial basis `fb1` (`FacetBasis` objects of the two degrees), over the part of the facet
+    whose normalised moments are `mom`, in longdouble.  'ghost': gamma h_avg^(1 + e) [dn u][dn v], 'jump':
+    gamma / h_avg [u][v]; h_avg as in `facet_tensor`."""
+    if fb0.verts != fb1.verts:
+        raise ValueError("two bases of one facet row")
+    if kind == "ghost":
+        gamma, e = (tuple(params) + (0.0,))[:2]
+        T = LD(gamma) * fb0.havg ** (1 + int(e)) * (fb0.dn_jump() @ mom.table(fb0.Af1, fb1.Af1) @ fb1.dn_jump().T)
+    elif kind == "jump":
+        T = LD(params[0]) / fb0.havg * (fb0.jump() @ mom.table(fb0.Af, fb1.Af) @ fb1.jump().T)
+    else:
+        raise ValueError(kind)
+    return fb0.area * T
+
+
 def facet_dofs(fb, poly, x, conn, row, degree):
     """Macro dof vector [cell 0, cell 1] of the functions poly[s](point) on the two cells (nodal values: vertices,
     then edge midpoints in Basix order)."""
@@ -859,6 +993,24 @@ def exact_facet_entries(key, cs, dofmap, bs, kind, degree, params, rows, cut_row
         return np.concatenate(R), np.concatenate(Cc), np.concatenate(Vv)
     tag = tuple(np.ascontiguousarray(a, dtype=np.int64).tobytes() for a in (rows, cut_rows, dofmap))
     return cached(("fentries", key, kind, degree, bs, tuple(params), one_point, tag), run)
+
+
+def exact_facet_entries2(key, cs, dofmap0, degree0, dofmap1, degree1, kind, params, rows):
+    """COO entries of an interior-facet term between two scalar spaces over the whole facets `rows`: rows by the test
+    space's dofs of the two cells, columns by the trial space's."""
+    whole = Moments(cs["tdim"] - 1)
+
+    def run():
+        R, Cc, Vv = [], [], []
+        for row in np.asarray(rows).reshape(-1, 4):
+            fb0, fb1 = facet_basis(key, cs, row, degree0), facet_basis(key, cs, row, degree1)
+            T = facet_tensor2(kind, fb0, fb1, whole, params).astype(np.float64)
+            d0 = np.concatenate([dofmap0[row[0]], dofmap0[row[2]]]).astype(np.int64)
+            d1 = np.concatenate([dofmap1[row[0]], dofmap1[row[2]]]).astype(np.int64)
+            R.append(np.repeat(d0, d1.size)); Cc.append(np.tile(d1, d0.size)); Vv.append(T.ravel())
+        return np.concatenate(R), np.concatenate(Cc), np.concatenate(Vv)
+    tag = tuple(np.ascontiguousarray(a, dtype=np.int64).tobytes() for a in (rows, dofmap0, dofmap1))
+    return cached(("fentries2", key, kind, degree0, degree1, tuple(params), tag), run)
 
 
 def exact_nitsche_entries(key, cs, dofmap, degree, gamma, rhs_scale=None):
