@@ -84,6 +84,19 @@ HOST_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32
                                C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64))
 
 
+class CGOptions(C.Structure):
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_iter", C.c_int32), ("check_every", C.c_int32),
+                ("precond", C.c_int32), ("lanes_per_row", C.c_int32)]
+
+
+class CGInfoStruct(C.Structure):
+    _fields_ = [("reason", C.c_int32), ("iterations", C.c_int32), ("residual_norm", C.c_double), ("rhs_norm", C.c_double)]
+
+
+PC_NONE, PC_JACOBI = 0, 1
+CG_CONVERGED, CG_MAX_ITER, CG_BREAKDOWN, CG_BAD_DIAGONAL = 1, 2, 3, 4
+
+
 class PatternView(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("nnz", C.c_int64), ("indptr", C.c_void_p),
                 ("indices", C.c_void_p), ("ncols", C.c_int64)]
@@ -106,7 +119,7 @@ SYMBOLS = [
     "cfx_space_static_bytes", "cfx_space_lattice_rows", "cfx_space_lattice_source_rows", "cfx_space_destroy", "cfx_form_create", "cfx_form_create2", "cfx_form_destroy", "cfx_form_prepare", "cfx_create_sparsity",
     "cfx_pattern_view_get", "cfx_pattern_reuse_stats", "cfx_pattern_destroy", "cfx_assemble_matrix", "cfx_assemble_matrix_zeroed", "cfx_assemble_vector", "cfx_assemble_scalar",
     "cfx_apply_lifting", "cfx_set_bc", "cfx_zero_rows", "cfx_csr_block_merge", "cfx_csr_permute", "cfx_tabulate_entity", "cfx_active_domain", "cfx_active_view", "cfx_deactivate_outside",
-    "cfx_active_destroy",
+    "cfx_active_destroy", "cfx_csr_spmv", "cfx_cg_options_default", "cfx_cg_solve",
     "cfx_dist_unique_id", "cfx_dist_comm_create", "cfx_dist_comm_create_host", "cfx_dist_comm_create_device", "cfx_dist_comm_info", "cfx_dist_comm_destroy",
     "cfx_dist_scatter_forward", "cfx_dist_scatter_reverse_add", "cfx_dist_scatter_reverse_matrix", "cfx_dist_indicator_or",
     "cfx_dist_indicator_forward",

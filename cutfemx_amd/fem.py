@@ -71,11 +71,16 @@ class Integral:
                              "(a list, each Function on its own space), not both")
 
     def _coefficient_values(self):
-        return None if self.coefficient is None else getattr(self.coefficient, "values", self.coefficient)
+        c = self.coefficient
+        if c is None or _lib.is_torch(c):   # (a torch tensor has a `values` METHOD: dof values in HBM are taken as they are)
+            return c
+        return getattr(c, "values", c)
 
     def _complex_coefficient(self) -> bool:
         v = self._coefficient_values()
-        return v is not None and np.iscomplexobj(v)
+        if v is None or _lib.is_torch(v) or isinstance(v, _lib.DeviceBuffer):   # (dof values in HBM are real)
+            return False
+        return np.iscomplexobj(v)
 
     def _cstruct(self, part: str = "re") -> _lib.Integral:
         keep = []
@@ -114,7 +119,7 @@ class Integral:
         coeff = None
         if self.coefficient is not None:
             values = self._coefficient_values()   # a Function or its dof array
-            if np.iscomplexobj(values):           # complex Function: its real / imaginary parts feed two real forms
+            if self._complex_coefficient():       # complex Function: its real / imaginary parts feed two real forms
                 values = np.ascontiguousarray(np.real(values) if part == "re" else np.imag(values), dtype=np.float64)
             coeff = _f64_ptr(values, keep)
         return _lib.Integral(itype, self.kernel, int(self.qdegree), stride, ent_ptr, n_ent,
@@ -718,6 +723,224 @@ def assemble_scalar(M: CutForm, out=None):
         raise ValueError("assemble_scalar: `out` goes with a rank-0 form")
     b = assemble_vector(M)
     return complex(b.sum()) if _is_complex(M.dtype) else float(b.sum())
+
+
+# ---- the solve in HBM: y = A x and Jacobi-preconditioned CG (cfx_csr_spmv / cfx_cg_solve) ----------------------------
+PC_NONE, PC_JACOBI = _lib.PC_NONE, _lib.PC_JACOBI
+CG_CONVERGED, CG_MAX_ITER, CG_BREAKDOWN, CG_BAD_DIAGONAL = (_lib.CG_CONVERGED, _lib.CG_MAX_ITER, _lib.CG_BREAKDOWN,
+                                                           _lib.CG_BAD_DIAGONAL)
+_CG_REASONS = {CG_CONVERGED: "converged", CG_MAX_ITER: "max_iter", CG_BREAKDOWN: "breakdown",
+               CG_BAD_DIAGONAL: "bad_diagonal"}
+
+
+@dataclass
+class CGInfo:
+    """cfx_cg_info: why cg_solve stopped, after how many updates of x, |r|_2 of the recurrence and |b|_2 (both over
+    the iterated rows)."""
+    reason: int
+    iterations: int
+    residual_norm: float
+    rhs_norm: float
+
+    @property
+    def converged(self) -> bool:
+        return self.reason == CG_CONVERGED
+
+    @property
+    def reason_name(self) -> str:
+        return _CG_REASONS.get(self.reason, "running")
+
+
+def cg_default_options() -> _lib.CGOptions:
+    """The defaults of cfx_cg_options_default (no GPU needed)."""
+    o = _lib.CGOptions()
+    _lib.check(_lib.load().cfx_cg_options_default(C.byref(o)))
+    return o
+
+
+def cg_info_buffer():
+    """A device buffer for `cg_solve(..., info_out=)`: 24 bytes that hold a cfx_cg_info; read with read_cg_info."""
+    return _lib.DeviceBuffer(3, np.float64)
+
+
+def read_cg_info(info_out) -> CGInfo:
+    """The CGInfo a cg_solve call left in `info_out` (one copy to the host)."""
+    raw = (info_out.numpy() if isinstance(info_out, _lib.DeviceBuffer) else info_out.cpu().numpy()).tobytes()
+    st = _lib.CGInfoStruct.from_buffer_copy(raw[:C.sizeof(_lib.CGInfoStruct)])
+    return CGInfo(int(st.reason), int(st.iterations), float(st.residual_norm), float(st.rhs_norm))
+
+
+def _csr_arrays(A):
+    """(nrows, indptr, indices, values) of a float64 MatrixCSR or MergedCSR: HBM addresses."""
+    if np.dtype(A.dtype) != np.dtype(np.float64):
+        raise TypeError("the solve takes float64 matrices (f32 and complex containers are out of scope)")
+    if isinstance(A, MergedCSR):
+        return A.nrows, A._indptr, A._indices, A._values
+    return A.nrows, A._view.indptr, A._view.indices, A.values_ptr   # (addresses alone: no count is needed)
+
+
+def _device_f64(a, n: int, what: str, keep: list):
+    """HBM address of n float64 values: a device torch tensor / DeviceBuffer as it stands, a host array uploaded."""
+    if _lib.is_device(a):
+        if (a.numel() if _lib.is_torch(a) else a.size) < n:
+            raise ValueError(f"{what} holds fewer than {n} values")
+        if _lib.is_torch(a):
+            import torch
+            if a.dtype != torch.float64 or not a.is_contiguous():
+                raise TypeError(f"{what} must be a contiguous float64 tensor")
+            keep.append(a)
+            return C.c_void_p(a.data_ptr())
+        return _lib.as_ptr(a, np.float64, keep)
+    h = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    if h.size < n:
+        raise ValueError(f"{what} holds fewer than {n} values")
+    d = _lib.DeviceBuffer(h.size, np.float64)
+    d.fill_from(h)
+    keep.append(d)
+    return C.c_void_p(d.ptr)
+
+
+def _row_list(rows, keep: list):
+    """(device pointer, count) of an int32 row list: device torch tensor / DeviceBuffer, or a host array uploaded."""
+    if rows is None:
+        return None, 0
+    if _lib.is_device(rows):
+        n = int(rows.numel()) if _lib.is_torch(rows) else rows.size
+        if _lib.is_torch(rows):
+            import torch
+            if rows.dtype != torch.int32 or not rows.is_contiguous():
+                rows = rows.to(torch.int32).contiguous()
+            keep.append(rows)
+            return C.c_void_p(rows.data_ptr()), n
+        return _lib.as_ptr(rows, np.int32, keep), n
+    h = np.ascontiguousarray(rows, dtype=np.int32).ravel()
+    d = _lib.DeviceBuffer(h.size, np.int32)
+    d.fill_from(h)
+    keep.append(d)
+    return C.c_void_p(d.ptr), h.size
+
+
+def csr_from_arrays(indptr, indices, values, ncols: int | None = None) -> "MergedCSR":
+    """A caller's CSR matrix (host arrays: indptr, indices, float64 values) copied into HBM as a MergedCSR, for spmv and
+    cg_solve.  ncols defaults to the number of rows."""
+    ip = np.ascontiguousarray(indptr, dtype=np.int64)
+    ix = np.ascontiguousarray(indices, dtype=np.int32)
+    va = np.ascontiguousarray(values, dtype=np.float64)
+    nrows, nnz = ip.size - 1, int(ip[-1]) if ip.size else 0
+    if nrows < 0 or ix.size < nnz or va.size < nnz:
+        raise ValueError("csr_from_arrays: indptr needs nrows + 1 entries, indices and values indptr[-1] entries")
+    ncols = nrows if ncols is None else int(ncols)
+    if nnz and (ix[:nnz].min() < 0 or ix[:nnz].max() >= ncols):
+        raise ValueError("csr_from_arrays: a column index lies outside [0, ncols)")
+    l, ptrs = _lib.lib(), []
+    for h in (ip, ix, va):
+        p = C.c_void_p()
+        _lib.check(l.cfx_device_alloc(C.byref(p), C.c_size_t(max(h.nbytes, 8))))
+        if h.nbytes:
+            _lib.check(l.cfx_copy(p, h.ctypes.data_as(C.c_void_p), C.c_size_t(h.nbytes)))
+        ptrs.append(p.value)
+    return MergedCSR(ptrs[0], ptrs[1], ptrs[2], nnz, nrows, ncols, np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64))
+
+
+def active_rows(domain: "ActiveDomain"):
+    """The rows of the active dofs of `domain` as an int32 device torch tensor, ascending: the complement of the
+    domain's inactive-dof list, formed on the device."""
+    import torch
+    from .dist import as_torch
+    V = domain.function_space
+    _lib.resolve_counts()
+    _, _, idf, ni = domain._view()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    mask = torch.ones(V.ndofs * V.bs, dtype=torch.bool, device=dev)
+    if ni > 0:
+        mask[as_torch(idf, ni, "int32", dev).long()] = False
+    return torch.nonzero(mask).reshape(-1).to(torch.int32)
+
+
+def spmv(A, x, out=None, rows=None, lanes_per_row: int = 0):
+    """y = A x in HBM (cfx_csr_spmv); `A` a float64 MatrixCSR or MergedCSR.  `x`: ncols values, `out`: nrows values
+    (allocated when None); device torch tensors / DeviceBuffers are used in place, a numpy `x` is uploaded and the product
+    comes back as numpy.  `rows`: only y[rows] is written.  lanes_per_row: 0 (chosen from the matrix) or 1, 4, 8, 16, 64."""
+    nrows, ip, ix, va = _csr_arrays(A)
+    keep: list = []
+    host = not _lib.is_device(x)
+    xp = _device_f64(x, A.ncols, "x", keep)
+    rp, nr = _row_list(rows, keep)
+    if out is None:
+        if _lib.is_torch(x) and not host:
+            import torch
+            out = torch.zeros(nrows, dtype=torch.float64, device=x.device)
+        else:
+            out = np.zeros(nrows) if host else _lib.DeviceBuffer(nrows, np.float64)
+            if not host:
+                _lib.check(_lib.lib().cfx_device_memset(C.c_void_p(out.ptr), 0, C.c_size_t(8 * nrows)))
+    yp = _device_f64(out, nrows, "out", keep)
+    _lib.check(_lib.lib().cfx_csr_spmv(C.c_int64(nrows), C.c_void_p(ip), C.c_void_p(ix), C.c_void_p(va), rp, C.c_int64(nr),
+                                       int(lanes_per_row), xp, yp))
+    if not _lib.is_device(out):      # a host `out`: the staged copy comes back (unlisted entries as they went in)
+        out[...] = keep[-1].numpy().reshape(out.shape)
+    return out
+
+
+def cg_solve(A, b, x0=None, *, rtol: float = 1e-10, atol: float = 0.0, max_iter: int | None = None,
+             precond: str = "jacobi", rows=None, domain=None, check_every: int | None = None, info_out=None,
+             lanes_per_row: int = 0):
+    """Solve A x = b by (Jacobi-)preconditioned conjugate gradients in HBM (cfx_cg_solve); returns (x, info).
+
+    `A`: a float64 MatrixCSR or MergedCSR, symmetric positive definite on the iterated rows.  `b`: numpy array or
+    device torch tensor; `x` comes back as the same kind (a new array; `x0` is not modified).  `rows` (int32 list, host or
+    device) or `domain` (an ActiveDomain: its active rows, listed on the device) restrict the solve: entries of x
+    outside the list keep the value of x0 (0 by default) and act as data.  Stops at |r| <= max(rtol |b|, atol).
+    `check_every`: how often the host looks at the state (None: the library's default); the result does not depend on it.
+    `info_out` (cg_info_buffer()): the cfx_cg_info stays in HBM, `info` is then info_out itself and -- with device
+    vectors and check_every = 0 -- the call makes no host round trip: exactly `max_iter` iterations are launched and the
+    ones after convergence return at once."""
+    nrows, ip, ix, va = _csr_arrays(A)
+    if A.ncols != nrows:
+        raise ValueError("cg_solve takes a square matrix")
+    if rows is not None and domain is not None:
+        raise ValueError("cg_solve: give `rows` or `domain`, not both")
+    pc = {"jacobi": PC_JACOBI, "none": PC_NONE, None: PC_NONE}.get(precond.lower() if isinstance(precond, str) else precond)
+    if pc is None:
+        raise ValueError("cg_solve: precond is 'jacobi' or 'none'")
+    o = cg_default_options()
+    o.rtol, o.atol, o.precond, o.lanes_per_row = float(rtol), float(atol), pc, int(lanes_per_row)
+    if max_iter is not None:
+        o.max_iter = int(max_iter)
+    if check_every is not None:
+        o.check_every = int(check_every)
+    keep: list = []
+    if domain is not None:
+        rows = active_rows(domain)
+    rp, nr = _row_list(rows, keep)
+    if _lib.is_torch(b) and b.is_cuda:
+        import torch
+        if b.dtype != torch.float64 or not b.is_contiguous() or b.numel() != nrows:
+            raise TypeError(f"b must be a contiguous float64 tensor of {nrows} values")
+        x = torch.zeros_like(b) if x0 is None else torch.as_tensor(x0, dtype=torch.float64, device=b.device).clone().contiguous()
+        bp, xp = C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr())
+    else:
+        if _lib.is_device(b) or _lib.is_device(x0):
+            raise TypeError("cg_solve: b (and x0) are numpy arrays or device torch tensors")
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.zeros(nrows) if x0 is None else np.array(x0, dtype=np.float64).ravel()
+        bp, xp = b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p)
+        if b.size != nrows:
+            raise ValueError(f"b must hold {nrows} values")
+    if (x.numel() if _lib.is_torch(x) else x.size) != nrows:
+        raise ValueError(f"x0 must hold {nrows} values")
+    l = _lib.lib()
+    if info_out is not None:
+        if not _lib.is_device(info_out):
+            raise TypeError("cg_solve: info_out is a device buffer (cg_info_buffer())")
+        ipn = _device_f64(info_out, 3, "info_out", keep)
+        _lib.check(l.cfx_cg_solve(C.c_int64(nrows), C.c_void_p(ip), C.c_void_p(ix), C.c_void_p(va), rp, C.c_int64(nr), bp, xp,
+                                  C.byref(o), ipn))
+        return x, info_out
+    st = _lib.CGInfoStruct()
+    _lib.check(l.cfx_cg_solve(C.c_int64(nrows), C.c_void_p(ip), C.c_void_p(ix), C.c_void_p(va), rp, C.c_int64(nr), bp, xp,
+                              C.byref(o), C.byref(st)))
+    return x, CGInfo(int(st.reason), int(st.iterations), float(st.residual_norm), float(st.rhs_norm))
 
 
 def zero_rows(A: MatrixCSR, *, tol: float = 0.0) -> np.ndarray:

@@ -64,6 +64,21 @@ def l2_error_form(system: PoissonSystem, V, uh, *, qdegree: int = 6):
                                   params=(fem.F_SINPROD, 1.0, 1.0), qdegree=qdegree, coefficient=uh)], V)
 
 
+def solve(system: PoissonSystem, V, **kw):
+    """Assemble, deactivate and solve the cut Poisson system without leaving HBM: A and b of `system`, diag = 1 / rhs = 0
+    on the dofs outside the active domain (fem.deactivate_outside), then Jacobi-preconditioned CG over the active rows
+    (fem.cg_solve, which takes `kw`: rtol, max_iter, check_every ...).  The whole path of
+    python/demo/demo_moving_poisson.py:53-67.  Returns (uh, info): uh a float64 device torch tensor with 0 on the inactive
+    dofs -- what l2_error_form(system, V, uh) and fem.assemble_scalar take."""
+    import torch
+    A = fem.assemble_matrix(system.a)
+    b = torch.zeros(V.ndofs * V.bs, dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
+    fem.assemble_vector(system.L, b)
+    domain = fem.active_domain(system.a)
+    fem.deactivate_outside(A, b, domain)
+    return fem.cg_solve(A, b, domain=domain, **kw)
+
+
 @dataclass
 class DGPoissonSystem:
     function_space: object

@@ -638,6 +638,61 @@ int cfx_deactivate_outside(cfx_active_t d, cfx_pattern_t pattern, double* values
                            double* b /* or NULL */, double diagonal, double rhs_value);
 int cfx_active_destroy(cfx_active_t d);
 
+/* ---- the solve: y = A x and Jacobi-preconditioned conjugate gradients on CSR arrays in HBM -----------------------
+ * What the reference's demos hand to PETSc after assembly (python/demo/demo_poisson.py:46-58,
+ * demo_moving_poisson.py:53-67).  FP64; the systems are symmetric positive definite -- the cut Poisson / elasticity
+ * systems after cfx_deactivate_outside.  The matrix is given by its raw CSR arrays (DEVICE pointers, the layout of
+ * cfx_pattern_view: indptr int64 [nrows + 1], indices int32, values double), so that the outputs of cfx_csr_block_merge
+ * and cfx_csr_permute are solved like an assembled MatrixCSR.  Column indices must lie inside the vectors.
+ *
+ * rows (a DEVICE list of n_rows distinct row numbers, or NULL: all rows; n_rows is then ignored): every kernel walks
+ * the listed rows alone.  cfx_csr_spmv writes y[rows] and no other entry of y.  cfx_cg_solve holds the entries of x
+ * outside the list fixed and never writes them; they enter r0 = b - A x0 and nothing else, so the call solves
+ * A[rows, rows] x[rows] = b[rows] - A[rows, others] x[others].
+ *
+ * lanes_per_row: lanes that share one row, 1, 4, 8, 16 or 64; 0 = chosen from the mean length of the iterated rows (on
+ * the device: no host round trip, but with a row list a pass over the list -- a caller that multiplies by one matrix many
+ * times passes the L).  Every sum has a fixed order: two calls on the same inputs give the same bits.
+ *
+ * cfx_csr_spmv: x and y are device pointers; rectangular matrices are fine.  The stream keeps running.
+ *
+ * cfx_cg_solve: b and x (nrows doubles each; x holds the start vector on entry and the solution on return) may be host
+ * or device pointers.  Stopping rule: |r|_2 <= max(rtol |b|_2, atol), r the recurrence residual, both norms over the
+ * iterated rows.  Every `reason` returns status 0; only bad arguments and HIP errors are error statuses.
+ *   CFX_CG_CONVERGED     the rule was met after `iterations` updates of x (0 when x0 already meets it; b = 0 with
+ *                        x0 = 0 gives x = 0)
+ *   CFX_CG_MAX_ITER      max_iter updates were made
+ *   CFX_CG_BREAKDOWN     p.Ap <= 0 (the matrix is not positive definite on the iterated rows): x is the iterate before
+ *   CFX_CG_BAD_DIAGONAL  CFX_PC_JACOBI met a listed row without a stored diagonal entry, or with a zero one: x = x0
+ * check_every: the host reads the state back every check_every iterations and stops launching once it is final.  x,
+ * `iterations` and the norms do not depend on it: iterations launched after the final one return at once.
+ * check_every = 0 launches exactly max_iter iterations; with a DEVICE `info` pointer the call then makes no host round
+ * trip at all (cfx_sync_count does not grow; usable inside cfx_step_begin / cfx_step_end with device b and x). */
+#define CFX_PC_NONE 0
+#define CFX_PC_JACOBI 1
+#define CFX_CG_CONVERGED 1
+#define CFX_CG_MAX_ITER 2
+#define CFX_CG_BREAKDOWN 3
+#define CFX_CG_BAD_DIAGONAL 4
+typedef struct
+{
+  double rtol, atol;
+  int32_t max_iter, check_every, precond, lanes_per_row;
+} cfx_cg_options;
+typedef struct
+{
+  int32_t reason, iterations;
+  double residual_norm, rhs_norm; /* |r|_2 of the recurrence at the last iterate, |b|_2: over the iterated rows */
+} cfx_cg_info;
+int cfx_csr_spmv(int64_t nrows, const int64_t* indptr, const int32_t* indices, const double* values,
+                 const int32_t* rows /* or NULL: all */, int64_t n_rows, int lanes_per_row /* 0: chosen */,
+                 const double* x, double* y);
+int cfx_cg_options_default(cfx_cg_options* opt); /* rtol 1e-10, atol 0, max_iter 10000, check_every 16, Jacobi, lanes 0;
+                                                    works without a GPU */
+int cfx_cg_solve(int64_t nrows, const int64_t* indptr, const int32_t* indices, const double* values,
+                 const int32_t* rows, int64_t n_rows, const double* b, double* x /* in: x0, out: x */,
+                 const cfx_cg_options* opt /* or NULL: the defaults */, cfx_cg_info* info /* host or device pointer */);
+
 /* ---- float32 instantiation of the boundary --------------------------------------------------------------
  * python/cutfemx/wrappers/fem.cpp:490-500 declares the runtime assembly for <T, U> in {float, double}^2 and
  * wrappers/cut.cpp:403-407 the cut API for float and double: T = scalar type of MatrixCSR / Vector / Function,

@@ -615,6 +615,45 @@ inline std::vector<std::int32_t> zero_rows(std::span<const double> values, const
   return out;
 }
 
+/// cfx_cg_options with the library's defaults (rtol 1e-10, Jacobi, check_every 16 ...)
+struct CGOptions : cfx_cg_options
+{
+  CGOptions() { check(cfx_cg_options_default(this)); }
+};
+
+/// y = A x in HBM (cfx_csr_spmv): `values`, `x`, `y` and the optional row list are DEVICE pointers; with `rows` only
+/// y[rows] is written.  lanes_per_row: 0 (chosen from the matrix), 1, 4, 8, 16 or 64.
+inline void spmv(const SparsityPattern& pattern, const double* values, const double* x, double* y,
+                 const std::int32_t* rows = nullptr, std::int64_t n_rows = 0, int lanes_per_row = 0)
+{
+  check(cfx_csr_spmv(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, lanes_per_row, x, y));
+}
+
+/// Jacobi-preconditioned conjugate gradients in HBM (cfx_cg_solve) on the symmetric positive definite system a
+/// deactivated cut problem gives: replaces the PETSc KSP of python/demo/demo_poisson.py:46-58.  `values` (and `rows`, the
+/// optional list of iterated rows) are device pointers; `b` and `x` (start vector in, solution out) host or device.
+/// Every reason (converged, max_iter, breakdown, bad diagonal) is returned in the info; only bad arguments throw.
+inline cfx_cg_info cg_solve(const SparsityPattern& pattern, const double* values, std::span<const double> b,
+                            std::span<double> x, const cfx_cg_options& options = CGOptions(),
+                            const std::int32_t* rows = nullptr, std::int64_t n_rows = 0)
+{
+  if ((std::int64_t)b.size() != pattern.view.nrows || x.size() != b.size() || pattern.view.ncols != pattern.view.nrows)
+    throw std::invalid_argument("cg_solve: a square matrix and one entry of b and x per row");
+  cfx_cg_info info{};
+  check(cfx_cg_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b.data(), x.data(),
+                     &options, &info));
+  return info;
+}
+/// ... with the cfx_cg_info left in HBM (`device_info`): with device `b` / `x` and options.check_every = 0 the call
+/// makes no host round trip
+inline void cg_solve(const SparsityPattern& pattern, const double* values, const double* b, double* x,
+                     const cfx_cg_options& options, cfx_cg_info* device_info, const std::int32_t* rows = nullptr,
+                     std::int64_t n_rows = 0)
+{
+  check(cfx_cg_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b, x, &options,
+                     device_info));
+}
+
 /// One block of a MatrixCSR block system: the values of A[i][j] with their pattern (nullptr: an absent block)
 struct MatrixBlock
 {
