@@ -672,6 +672,22 @@ struct Stencil
   double lat_src_T[kLatSrcDegrees][8] = {};
   bool lat_src_T_built[kLatSrcDegrees] = {};
   DevArray<unsigned long long> lat_src_written;
+  // lat_shell_ran: hexes the shell form of the hex kernel ran in the last assembly of a linear form on this space
+  // (Stencil::shell_bits below; diagnostics only).  The mark pass of an assembly zeroes it, the hex kernel adds one
+  // number per block; lat_shell_counted: it may hold a number (an assembly that does not take the path zeroes it then).
+  DevArray<unsigned long long> lat_shell_ran;
+  mutable bool lat_shell_counted = false;
+  // Shell hexes of the source integral of the assembly under way (cfx::source_shell_hexes): bit h is set by the rows
+  // that do not take the closed form for every hex h = cell / 6 that holds a marked cell around them.  One bit per hex
+  // of the mesh (17 MB at 512^3), zero between assemblies: the compaction clears every word it reads, so no plan and
+  // no assembly pays a fill (it lives with the space for that reason: a step's plan is a new one).  shell_dirty: an
+  // assembly left between the mark pass and the compaction (an error); the next one fills zeros first.
+  // ASSUMES one linear form of the space under assembly at a time: the bit set, the counter above and these flags are
+  // scratch of the assembly under way, shared by every form on the space (hence mutable in a table handed out const).
+  // Two linear forms of ONE space on the two lanes of an overlap section would race on them; no caller does that
+  // (an overlap section pairs a linear form with a bilinear one), and nothing here orders the lanes against it.
+  mutable DevArray<unsigned long long> shell_bits;
+  mutable bool shell_dirty = false;
   // The single-pass build of the neighbour lists stages 64 columns per dof (34 GB at 512^3).  Giving that block back to
   // the driver made the NEXT large hipMalloc of the process take 1.5 - 2.6 s on this stack (tools/time_malloc.py: 0.2 ms
   // for the first 34 GB, 1.8 s for the same request after a hipFree of 34 GB); left in the block cache it would sit
@@ -1040,7 +1056,9 @@ const Stencil& space_stencil_tiles(cfx_space_s* V);                     // cfx_r
 const Stencil& space_lattice(cfx_space_s* V);                           // cfx_rowasm.hip (Stencil::lat_rows)
 bool lattice_template(cfx_space_s* V);                                  // cfx_gather.hip (Stencil::lat_tmpl)
 const double* lattice_source_moments(cfx_space_s* V, int qdegree);      // cfx_rowasm.hip (Stencil::lat_src_T; null: none)
-bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits);          // cfx_rowasm.hip (cfx_row_plan::lat_tile_first)
+bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits);
+void lattice_tile_lists(cfx_form_s* a, int64_t* n_plain, int64_t* n_tiles, int32_t* plain_rows, uint8_t* templ,
+                        int32_t* tile_first, int32_t* tile_id);         // cfx_rowasm.hip (cfx_form_lattice_tile_lists)          // cfx_rowasm.hip (cfx_row_plan::lat_tile_first)
 bool space_dof_verts(cfx_space_s* V);                                   // cfx_rowasm.hip (cfx_space_s::dof_verts)
 bool plain_vec_offsets(cfx_form_s* L, uint8_t mark);                    // cfx_rowasm.hip
 bool source_groups_ok(cfx_form_s* L, uint8_t mark);                     // cfx_gather.hip

@@ -1910,6 +1910,28 @@ int cfx_space_lattice_source_rows(cfx_space_t V, int64_t* rows)
   CFX_API_END
 }
 
+int cfx_space_source_shell_hexes(cfx_space_t V, int64_t* hexes)
+{
+  CFX_API_BEGIN
+  require(V && hexes, CFX_ERR_INVALID_ARGUMENT, "cfx_space_source_shell_hexes: null argument");
+  *hexes = 0;
+  // (a query builds nothing: without the lattice table of the space no assembly can have taken the path)
+  const cfx::Stencil& S = V->stencil;
+  if (S.lat_built && S.lat_rows > 0 && S.lat_shell_ran.p) *hexes = (int64_t)cfx::read_scalar(S.lat_shell_ran.p);
+  CFX_API_END
+}
+
+int cfx_form_lattice_tile_lists(cfx_form_t a, int64_t* n_plain, int64_t* n_tiles, int32_t* plain_rows, uint8_t* templ,
+                                int32_t* tile_first, int32_t* tile_id)
+{
+  CFX_API_BEGIN
+  require(a && n_plain && n_tiles, CFX_ERR_INVALID_ARGUMENT, "cfx_form_lattice_tile_lists: null argument");
+  *n_plain = 0; *n_tiles = -1;
+  if (a->rank == 0 || !a->plan) return CFX_OK;
+  cfx::lattice_tile_lists(a, n_plain, n_tiles, plain_rows, templ, tile_first, tile_id);
+  CFX_API_END
+}
+
 int cfx_space_destroy(cfx_space_t V)
 {
   CFX_API_BEGIN

@@ -686,10 +686,158 @@ struct GroupHead
 
 struct GroupArgs
 {
-  const int32_t* first; // [ng] position of the hex's first entity in A.entities
+  const int32_t* first; // [ng] position of the hex's first entity in A.entities (SHELL: the hex id itself)
   DevN ng;
   int64_t cap;          // corner plane stride of A.t2 (cfx_row_plan::vec_group_cap)
+  // SHELL: the integral's entity bit set and ranks (cfx_row_plan::std_bits / std_rank) and the counter of hexes run
+  const unsigned long long* bits = nullptr;
+  const int32_t* rank = nullptr;
+  unsigned long long* ran = nullptr;
 };
+
+// Shell hexes of the source integral with mark bit `mark` (Stencil::shell_bits).  A block takes kBlock entries of the
+// two row lists, one after the other: every special row, and every plain row that does not take the closed form
+// (lattice_source_row), is queued in LDS (phase A, one lane per entry); then 32 lanes take a queued row, one incident
+// cell each, and set the bit of hex cell / 6 for every marked cell (phase B).  Those are the hexes with a marked tet
+// that has such a row for a corner, the only ones whose corner sums or per-cell records anybody reads.
+// Both phases are chains of dependent loads, so what counts is how many are in flight (512^3, DESIGN.md section 3
+// round 9): one lane per row walking its 24 cells 0.44 ms; 32 lanes per row, one row per lane group at a time
+// 0.18 ms; kShellMarkRows rows per group at a time, each step of the chain requested for all of them before the
+// first is used: 0.17 ms.  Four list entries per lane in phase A on top of that: 0.25 ms, not kept.
+// A row's cells ascend, the tets of a hex follow each other: a lane whose left neighbour marked the same hex, or that
+// sees the bit set already, saves the atomic.  32-bit halves of the 64-bit words (little endian).  The first thread
+// zeroes the counter of the hex kernel that follows.
+constexpr int kShellMarkRows = 4;
+__global__ void __launch_bounds__(kBlock) source_shell_mark_kernel(DevN n_special_d, const int32_t* __restrict__ special,
+                                                                   DevN n_plain_d, const int32_t* __restrict__ plain,
+                                                                   const int32_t* __restrict__ t2off,
+                                                                   const uint8_t* __restrict__ diagpos,
+                                                                   const int64_t* __restrict__ d2c_off,
+                                                                   const int32_t* __restrict__ d2c,
+                                                                   const uint8_t* __restrict__ cellmark, uint8_t mark,
+                                                                   unsigned int* __restrict__ bits32, int64_t nhex,
+                                                                   unsigned long long* __restrict__ ran)
+{
+  __shared__ int32_t s_rows[kBlock];
+  __shared__ int s_n;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i == 0) *ran = 0ull;
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  int32_t r = -1;
+  if (i < n_special_d.cap)
+  {
+    if (i < dev_n(n_special_d)) r = special[i];
+  }
+  else if (i - n_special_d.cap < dev_n(n_plain_d))
+  {
+    r = plain[i - n_special_d.cap];
+    if (lattice_source_row(t2off[r], diagpos[r])) r = -1;
+  }
+  if (r >= 0) s_rows[atomicAdd(&s_n, 1)] = r;
+  __syncthreads();
+  constexpr int U = kShellMarkRows, NG = kBlock / 32;
+  const int nq = s_n, k = threadIdx.x & 31;
+  // the hex of cell c if it is marked, else -1; then the atomic unless the left neighbour or the word says it is done
+  auto hex_of = [&](int32_t c) -> int64_t { return c >= 0 && (cellmark[c] & mark) && c / 6 < nhex ? (int64_t)(c / 6) : -1; };
+  for (int q0 = threadIdx.x >> 5; q0 < nq; q0 += NG * U)
+  {
+    int64_t e0[U], e1[U], h[U];
+    int32_t c[U];
+    bool todo[U];
+    unsigned w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+    {
+      const int q = q0 + u * NG;
+      e0[u] = 0; e1[u] = 0;
+      if (q < nq) { const int64_t row = s_rows[q]; e0[u] = d2c_off[row]; e1[u] = d2c_off[row + 1]; }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) c[u] = e0[u] + k < e1[u] ? d2c[e0[u] + k] : -1;
+#pragma unroll
+    for (int u = 0; u < U; ++u) h[u] = hex_of(c[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+    {
+      const int64_t left = __shfl_up(h[u], 1, 32);
+      todo[u] = h[u] >= 0 && !(k > 0 && left == h[u]);
+      w[u] = todo[u] ? bits32[h[u] >> 5] : ~0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (todo[u] && !(w[u] & (1u << (h[u] & 31)))) atomicOr(&bits32[h[u] >> 5], 1u << (h[u] & 31));
+    // (a row of more than 32 cells: the rest of them, a cell per lane again)
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      for (int64_t e = e0[u] + 32 + k; e < e1[u]; e += 32)
+      {
+        const int64_t hh = hex_of(d2c[e]);
+        if (hh >= 0 && !(bits32[hh >> 5] & (1u << (hh & 31)))) atomicOr(&bits32[hh >> 5], 1u << (hh & 31));
+      }
+  }
+}
+
+// The set bits of the shell bit set as an ascending list of hex ids; every word read is cleared.  A thread owns `per`
+// consecutive words (thread-major: the list ascends), a block kBlock * per of them.  count: the block totals (any order
+// of the words does); write: offsets from the scan of those totals -- or, inside a sync-free step, count + offsets +
+// write in this one launch with the tiles chained (compact_chained_kernel).  Nothing is stored at or beyond `cap`.
+struct ShellWords
+{
+  unsigned long long* words;
+  int64_t nwords;
+  int per;
+};
+
+__global__ void __launch_bounds__(kBlock) source_shell_count_kernel(ShellWords S, int32_t* __restrict__ tile_counts)
+{
+  const int64_t base = (int64_t)blockIdx.x * kBlock * S.per;
+  int c = 0;
+  for (int k = 0; k < S.per; ++k)
+  {
+    const int64_t i = base + (int64_t)k * kBlock + threadIdx.x;
+    if (i < S.nwords) c += __popcll(S.words[i]);
+  }
+  int total;
+  (void)block_exclusive_scan<int>(c, total);
+  if (threadIdx.x == 0) tile_counts[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(kBlock) source_shell_write_kernel(ShellWords S, const int64_t* __restrict__ tile_offsets,
+                                                                    int32_t* __restrict__ out, int64_t cap, ChainState chain,
+                                                                    int64_t* __restrict__ total_out, CountJobs after)
+{
+  const unsigned int tile = chain.state ? chain_take_tile(chain.ticket) : blockIdx.x;
+  const int64_t base = ((int64_t)tile * kBlock + threadIdx.x) * S.per;
+  int c = 0;
+  for (int k = 0; k < S.per; ++k)
+    if (base + k < S.nwords) c += __popcll(S.words[base + k]);
+  int total;
+  const int off = block_exclusive_scan<int>(c, total);
+  int64_t prefix;
+  if (chain.state) prefix = (int64_t)chain_exclusive_prefix(chain.state, tile, (unsigned long long)total);
+  else prefix = tile_offsets[tile];
+  int64_t o = prefix + off;
+  if (c > 0)
+    for (int k = 0; k < S.per; ++k)
+    {
+      const int64_t i = base + k;
+      unsigned long long w = i < S.nwords ? S.words[i] : 0ull;
+      if (w == 0ull) continue;
+      S.words[i] = 0ull;
+      while (w)
+      {
+        if (o < cap) out[o] = (int32_t)(i * 64 + __builtin_ctzll(w));
+        ++o;
+        w &= w - 1ull;
+      }
+    }
+  if (chain.state && tile == gridDim.x - 1 && threadIdx.x == kBlock - 1)
+  {
+    *total_out = prefix + total;
+    if (after.n > 0) count_publish(after);
+  }
+}
 
 // LATTICE = false: one lane per group entry.
 // LATTICE = true (the closed-form source term is on; diagpos = Stencil::diagpos): most hexes are bulk -- all 8 corner
@@ -701,16 +849,47 @@ struct GroupArgs
 // the corner sums of closed-form rows.  The queue order is arbitrary: a hex writes its own slots only.  (The body
 // stands in the kernel itself, as the one pass of a do-loop without LATTICE: as a function of its own the same text
 // spills a register.)
-template <bool LATTICE>
-__global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_source_groups_kernel(VecArgs A, GroupArgs G, const uint8_t* __restrict__ diagpos)
+// SHELL (with LATTICE; cfx::source_shell_hexes): G.first is the list of shell hexes itself, found from the rows that read
+// them: one lane per hex, no phase A and no queue.  The marked tets of the hex are the six bits at 6 * hex of the
+// integral's entity bit set (they may straddle two words), the list position of the first of them is its rank: the
+// same mask and the same `f` the group list gives, so the body -- tet order, arithmetic, store predicates -- is the
+// one below and b comes out bit for bit.  The hexes run are counted with one atomic per block.
+#ifndef CFX_SOURCE_SHELL_WAVES
+#define CFX_SOURCE_SHELL_WAVES 3 // (waves per SIMD of the SHELL form, 512^3: 3 -> 0.257 ms with 141 VGPRs, 4 -> 0.273 ms with 128; 5 and 6 spill: 0.40, 0.43 ms)
+#endif
+template <bool LATTICE, bool SHELL = false>
+__global__ void __launch_bounds__(kBlock, SHELL ? CFX_SOURCE_SHELL_WAVES : CFX_SOURCE_WAVES)
+vec_source_groups_kernel(VecArgs A, GroupArgs G, const uint8_t* __restrict__ diagpos)
 {
-  __shared__ int32_t s_queue[LATTICE ? kBlock : 1];
+  static_assert(LATTICE || !SHELL, "the shell list serves the closed-form path");
+  __shared__ int32_t s_queue[LATTICE && !SHELL ? kBlock : 1];
   __shared__ int s_n;
   int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   int q = threadIdx.x, nq = 0;
+  int32_t shell_hex = 0;
+  unsigned shell_mask = 0;
   if constexpr (!LATTICE)
   {
     if (g >= dev_n(G.ng)) return;
+  }
+  else if constexpr (SHELL)
+  {
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    if (g < dev_n(G.ng))
+    {
+      shell_hex = G.first[g];
+      const int64_t c0 = 6 * (int64_t)shell_hex;
+      const int sh = (int)(c0 & 63);
+      unsigned long long m = G.bits[c0 >> 6] >> sh;
+      if (sh > 58) m |= G.bits[(c0 >> 6) + 1] << (64 - sh); // (cells 6h .. 6h + 5 reach into the next word, which exists)
+      shell_mask = (unsigned)m & 63u;
+    }
+    const int ran = __popcll(__ballot(shell_mask != 0));
+    if ((threadIdx.x & 63) == 0 && ran) atomicAdd(&s_n, ran);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_n) atomicAdd(G.ran, (unsigned long long)s_n);
+    if (shell_mask == 0) return;
   }
   else
   {
@@ -731,21 +910,33 @@ __global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_source_groups_ke
   }
   do
   {
-    if constexpr (LATTICE)
+    if constexpr (LATTICE && !SHELL)
     {
       if (q >= nq) break;
       g = (int64_t)blockIdx.x * kBlock + s_queue[q];
       q += kBlock;
     }
-    const int64_t n = dev_n(A.n), f = G.first[g];
-    int32_t ids[6];
-#pragma unroll
-    for (int m = 0; m < 6; ++m) ids[m] = A.entities[f + m < n ? f + m : n - 1];
-    const int32_t hex = ids[0] / 6;
+    int64_t f;
+    int32_t hex;
     unsigned mask = 0;
+    if constexpr (SHELL)
+    {
+      hex = shell_hex;
+      mask = shell_mask;
+      f = entity_index(G.bits, G.rank, 6 * (int64_t)hex + __builtin_ctz(mask));
+    }
+    else
+    {
+      const int64_t n = dev_n(A.n);
+      f = G.first[g];
+      int32_t ids[6];
 #pragma unroll
-    for (int m = 0; m < 6; ++m)
-      if (f + m < n && ids[m] / 6 == hex) mask |= 1u << (ids[m] - 6 * hex);
+      for (int m = 0; m < 6; ++m) ids[m] = A.entities[f + m < n ? f + m : n - 1];
+      hex = ids[0] / 6;
+#pragma unroll
+      for (int m = 0; m < 6; ++m)
+        if (f + m < n && ids[m] / 6 == hex) mask |= 1u << (ids[m] - 6 * hex);
+    }
     // the eight corners from tets 0 {0,1,3,7}, 3 {0,2,6,7} and 4 {0,4,5,7}
     const int4* conn4 = reinterpret_cast<const int4*>(A.conn) + 6 * (int64_t)hex;
     const int4 r0 = conn4[0], r3 = conn4[3], r4 = conn4[4];
@@ -814,7 +1005,7 @@ __global__ void __launch_bounds__(kBlock, CFX_SOURCE_WAVES) vec_source_groups_ke
       }
       else if (plain & (1u << k)) A.t2[(int64_t)k * G.cap + A.t2off[sv[k]] - 1] = acc[k];
     }
-  } while (LATTICE);
+  } while (LATTICE && !SHELL);
 }
 
 // ---------------------------------------------------------------------------
@@ -3931,9 +4122,66 @@ void vec_block_partials(cfx_form_s* L, const cfx_integral_dev* Istd, uint8_t mar
   }
 }
 
+// The shell hexes of the source integral in cell slot `slot` as an ascending list (Stencil::shell_bits): marked by
+// the rows that do not take the closed form (source_shell_mark_kernel: a launch of its own over the special and the
+// plain rows -- the plan's plain-row pass runs once per plan, the marks are used up once per assembly), then
+// compacted.  The length is the count site vec.shell_hexes: read back here outside a step, the previous step's
+// capacity inside one (an overflow voids the step).  The bit set is zero again when the compaction has run.
+constexpr int64_t kSourceShellMinEntities = 4000000; // (entities of the integral from which the shell path is taken)
+inline Count source_shell_hexes(cfx_form_s* L, int slot, const uint8_t* diagpos, DevArray<int32_t>& hexes)
+{
+  cfx_space_s* V = L->V;
+  cfx_row_plan& plan = row_plan(L);
+  const char* site = "vec.shell_hexes";
+  const int64_t nhex = V->mesh->ncells / 6, nwords = (nhex + 63) / 64;
+  const int64_t nrows = plan.n_special_rows.cap() + plan.n_plain_rows.cap();
+  const Stencil& stn = space_stencil(V);
+  if (nwords == 0 || nrows == 0)
+  {
+    hexes.alloc(0);
+    step_record(site, 0);
+    dev_fill(stn.lat_shell_ran.p, 0, sizeof(unsigned long long));
+    return Count(0);
+  }
+  if (stn.shell_bits.n != nwords) { stn.shell_bits.alloc(nwords); stn.shell_dirty = true; }
+  if (stn.shell_dirty) stn.shell_bits.zero();
+  stn.shell_dirty = true;
+  const Adjacency& adj = V->dof_cells();
+  const DevN n_special = plan.n_special_rows, n_plain = plan.n_plain_rows;
+  launch("source_shell", source_shell_mark_kernel, grid_for(nrows), dim3(kBlock), 0, n_special, plan.special_rows.p, n_plain,
+         plan.plain_rows.p, plan.vec_t2off.p, diagpos, adj.offsets.p, adj.cells.p, plan.cellmark.p, (uint8_t)(1u << slot),
+         reinterpret_cast<unsigned int*>(stn.shell_bits.p), nhex, stn.lat_shell_ran.p);
+  // tiles of kBlock * per words: `per` keeps a large mesh within the tiles of one chained launch (512^3: 16)
+  const int per = (int)std::min<int64_t>(64, std::max<int64_t>(1, (nwords + 512 * kBlock - 1) / (512 * kBlock)));
+  const int64_t ntiles = (nwords + (int64_t)kBlock * per - 1) / ((int64_t)kBlock * per);
+  const ShellWords W{stn.shell_bits.p, nwords, per};
+  DevArray<int32_t> counts;
+  DevArray<int64_t> offsets(ntiles + 1);
+  Count total;
+  const CountSource src{offsets.p + ntiles, kCountI64, kCountUpTo};
+  CountPlan cp(1, &site, &src);
+  const ChainState chain = fused_chain(cp.publish, ntiles);
+  CountJobs after{};
+  if (chain.state) after = cp.take_jobs();
+  else
+  {
+    counts.alloc(ntiles);
+    launch("source_groups", source_shell_count_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, W, counts.p);
+    exclusive_scan(counts.p, offsets.p, ntiles, &cp);
+  }
+  cp.finish(&total);
+  hexes.alloc(total.cap());
+  if (total.cell) hexes.count = total;
+  launch("source_groups", source_shell_write_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, W, offsets.p, hexes.p, total.cap(),
+         chain, offsets.p + ntiles, after);
+  stn.shell_dirty = false;
+  stn.lat_shell_counted = true;
+  return total;
+}
+
 template <int TDIM, int DEG>
 void vec_tensors(cfx_form_s* L, const cfx_integral_dev& I, bool runtime, double* out, double* t2 = nullptr, int64_t out_cells = 0,
-                 const uint8_t* lat_src = nullptr)
+                 const uint8_t* lat_src = nullptr, int slot = -1)
 {
   cfx_space_s* V = L->V;
   if (user_integrand_known(I.kernel))
@@ -3957,9 +4205,28 @@ void vec_tensors(cfx_form_s* L, const cfx_integral_dev& I, bool runtime, double*
     cfx_row_plan& plan = row_plan(L);
     if (TDIM == 3 && DEG == 1 && A.t2 && plan.vec_groups && source_series_ok<DEG>(V, I))
     {
-      // by hex (the staging was laid out for it: cfx::plain_vec_offsets): the group list is the positions of the entities
-      // that start a hex, compacted from the list itself (ascending and without repeats: a located list)
+      // by hex (the staging was laid out for it: cfx::plain_vec_offsets).  With the closed form on the lattice rows and
+      // the entity bit set of the slot at hand, the hexes that somebody reads come from the rows that read them
+      // (CFX_SOURCE_SHELL=0: sifted from the whole list as below)
       DevArray<int32_t> first;
+      // ... where the list is long enough to pay for it: at 128^3 (1.5 M entities) mark pass + list + body cost 0.066 ms
+      // against 0.054 ms for the sift and the step was 0.015 ms slower, at 512^3 (99 M) 0.46 against 1.08 ms
+      // (DESIGN.md section 3 round 9).  CFX_SOURCE_SHELL=2: whatever the length (tests); =0: never
+      const char shell_sw = env_char<Sw::SOURCE_SHELL>();
+      const bool shell_on = shell_sw == '2' || (shell_sw != '0' && I.n_entities.hint() >= kSourceShellMinEntities);
+      if (lat_src && slot >= 0 && plan.std_bits[slot].p && plan.std_rank[slot].p && space_stencil(V).lat_shell_ran.p && shell_on)
+      {
+        const Count ns = source_shell_hexes(L, slot, lat_src, first);
+        GroupArgs G{first.p, ns.devn(), plan.vec_group_cap};
+        G.bits = reinterpret_cast<const unsigned long long*>(plan.std_bits[slot].p);
+        G.rank = plan.std_rank[slot].p;
+        G.ran = space_stencil(V).lat_shell_ran.p;
+        if (ns.cap() > 0)
+          launch("vec_tensors_std", vec_source_groups_kernel<true, true>, grid_for(ns.cap()), dim3(kBlock), 0, A, G, lat_src);
+        return;
+      }
+      // ... else the group list is the positions of the entities that start a hex, compacted from the list itself
+      // (ascending and without repeats: a located list)
       const Count ng = compact_count("source_groups", "vec.source_groups", A.n, GroupHead{A.entities}, first);
       GroupArgs G{first.p, ng.devn(), plan.vec_group_cap};
       if (ng.cap() > 0 && lat_src) // (the closed form serves the bulk rows: Stage1::lat_src)
@@ -4071,7 +4338,7 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
       R.std_by_cell = by_cell ? 1 : 0;
       if (a->rank == 2) dump_integral(a, ii, 1, st.buffers.back().p);
       else if constexpr (BS == 1)
-        vec_tensors<TDIM, DEG>(a, I, false, st.buffers.back().p, st.vec_t2, by_cell ? V->mesh->ncells : 0, st.lat_src);
+        vec_tensors<TDIM, DEG>(a, I, false, st.buffers.back().p, st.vec_t2, by_cell ? V->mesh->ncells : 0, st.lat_src, s);
     }
     const int64_t n_rules = I.rules ? I.rules->nr.cap() : 0;
     if (n_rules > 0 && combine_cuts)
@@ -4779,6 +5046,11 @@ void run_vector(cfx_form_s* L, double* b)
 {
   Stage1 st;
   cfx_row_plan& plan = row_plan(L);
+  // (the shell-hex counter speaks of the last assembly: one that does not take the path leaves 0 behind.  The member
+  // itself, not space_stencil(): a form that needs no stencil must not build one for a host flag)
+  const Stencil& shell_stn = L->V->stencil;
+  const bool shell_counted = shell_stn.lat_shell_counted;
+  shell_stn.lat_shell_counted = false;
   // one integral with uncut entities (the volume term)
   int slot = -1, count = 0;
   for (int s = 0; s < plan.n_cell_slots; ++s)
@@ -4820,6 +5092,7 @@ void run_vector(cfx_form_s* L, double* b)
   }
   RowArgs A = prepare<TDIM, DEG>(L, st);
   A.values = b;
+  if (shell_counted && !shell_stn.lat_shell_counted) dev_fill(shell_stn.lat_shell_ran.p, 0, sizeof(unsigned long long));
   if (st.vec_blocks)
   {
     st.part.alloc(plan.vb_total);

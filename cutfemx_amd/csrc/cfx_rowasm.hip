@@ -2874,6 +2874,8 @@ const Stencil& space_lattice(cfx_space_s* V)
     S.lat_written.zero();
     S.lat_src_written.alloc(1);
     S.lat_src_written.zero();
+    S.lat_shell_ran.alloc(1);
+    S.lat_shell_ran.zero();
     S.lat_rstar = (int64_t)h[1];
     S.lat_sb0 = (int64_t)h[4];
     S.lat_rel = (int)((int64_t)h[5] - (int64_t)h[4]);
@@ -3007,6 +3009,173 @@ struct LatTileStart
   }
 };
 
+// The write pass of the two tile lists (TileStart, LatTileStart) of one index range: compact_write2_n_kernel with the
+// two predicates decided from wavefront ballots.  LatTileStart::operator() walks back over up to 15 earlier rows of
+// the tile, three loads each, for every list entry, in a pass whose lanes own 8 consecutive entries (0.22 ms at
+// 512^3).  Here every entry's "tile starts" and "not a template row" bits are evaluated once, coalesced, and kept as
+// ballot words in LDS (the block's kTile entries behind a halo of the 16 entries before them: a tile has at most
+// kRowTile rows).  Entry i is the first non-template row of its tile iff its own bit is set and no bit is set from
+// the tile's start -- the nearest "tile starts" bit at or before i, at most 15 back -- to i - 1.
+static_assert(kRowTile == 16, "the 16-entry halo and windows of tile_lists_write_kernel");
+__global__ void __launch_bounds__(kBlock) tile_lists_write_kernel(DevN n_d, LatTileStart lat, TileIdEmit ea, TileIdEmit eb,
+                                                                  const int64_t* __restrict__ tile_offsets,
+                                                                  int32_t* __restrict__ outA, int64_t capA,
+                                                                  int32_t* __restrict__ outB, int64_t capB, ChainState chain,
+                                                                  int64_t* __restrict__ total_out, CountJobs after)
+{
+  // bit r of the arrays: entry tbase - 64 + r (word 0: the halo, its top 16 bits; words 1 .. kTile / 64: the block)
+  __shared__ unsigned long long s_ts[kTile / 64 + 2], s_nt[kTile / 64 + 2];
+  const int64_t n = dev_n(n_d);
+  const unsigned int tile = chain.state ? chain_take_tile(chain.ticket) : blockIdx.x;
+  const int64_t tbase = (int64_t)tile * kTile;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  auto flags = [&](int64_t i, bool& ts, bool& nt)
+  {
+    ts = false; nt = false;
+    if (i >= 0 && i < n)
+    {
+      ts = i == 0 || (lat.rows[i] / kRowTile) != (lat.rows[i - 1] / kRowTile);
+      nt = !lat.templ(i);
+    }
+  };
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k)
+  {
+    const int chunk = k * (kBlock / 64) + wave;
+    bool ts, nt;
+    flags(tbase + (int64_t)chunk * 64 + lane, ts, nt);
+    const unsigned long long bt = __ballot(ts), bn = __ballot(nt);
+    if (lane == 0) { s_ts[1 + chunk] = bt; s_nt[1 + chunk] = bn; }
+  }
+  if (wave == 0)
+  {
+    bool ts, nt;
+    flags(lane >= 48 ? tbase - 64 + lane : -1, ts, nt);
+    const unsigned long long bt = __ballot(ts), bn = __ballot(nt);
+    if (lane == 0) { s_ts[0] = bt; s_nt[0] = bn; s_ts[kTile / 64 + 1] = 0ull; s_nt[kTile / 64 + 1] = 0ull; }
+  }
+  __syncthreads();
+  // the lane's 8 consecutive entries: bits lo .. lo + 22 of the arrays, lo = 15 before its first entry
+  const int lo = 64 + (int)threadIdx.x * kScanItems - 15, wd = lo >> 6, sh = lo & 63;
+  auto window = [&](const unsigned long long* a) -> unsigned
+  {
+    unsigned long long v = a[wd] >> sh;
+    if (sh) v |= a[wd + 1] << (64 - sh);
+    return (unsigned)v & 0x7fffffu;
+  };
+  const unsigned wts = window(s_ts), wnt = window(s_nt);
+  const int64_t base = tbase + (int64_t)threadIdx.x * kScanItems;
+  bool fa[kScanItems], fb[kScanItems];
+  int64_t c = 0;
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k)
+  {
+    fa[k] = (wts >> (15 + k)) & 1u;
+    const unsigned t16 = (wts >> k) & 0xffffu;            // "tile starts" of entries i - 15 .. i
+    const int q = t16 ? 31 - __clz((int)t16) : 0;          // the tile of entry i starts 15 - q entries back
+    const unsigned before = ((wnt >> k) & 0x7fffu) >> q;   // non-template rows from there to i - 1
+    fb[k] = ((wnt >> (15 + k)) & 1u) && before == 0u;
+    c += (fa[k] ? 1ll : 0ll) + (fb[k] ? (1ll << 32) : 0ll);
+  }
+  int64_t total;
+  const int64_t off = block_exclusive_scan<int64_t>(c, total);
+  int64_t prefix;
+  if (chain.state) prefix = (int64_t)chain_exclusive_prefix(chain.state, tile, (unsigned long long)total);
+  else prefix = tile_offsets[tile];
+  int64_t oa = ((prefix + off) & 0xffffffffll), ob = ((prefix + off) >> 32);
+#pragma unroll
+  for (int k = 0; k < kScanItems; ++k)
+  {
+    if (fa[k]) { if (oa < capA) { outA[oa] = (int32_t)(base + k); ea(oa, base + k); } ++oa; }
+    if (fb[k]) { if (ob < capB) { outB[ob] = (int32_t)(base + k); eb(ob, base + k); } ++ob; }
+  }
+  if (chain.state && tile == gridDim.x - 1 && threadIdx.x == kBlock - 1)
+  {
+    *total_out = prefix + total;
+    if (after.n > 0) count_publish(after);
+  }
+}
+
+// compact_count_pair for (TileStart, LatTileStart) with the write pass above
+static void compact_tile_lists(const char* name, const char* const sites[2], DevN n, const LatTileStart& lat, TileIdEmit& ea,
+                               TileIdEmit& eb, DevArray<int32_t>& outA, DevArray<int32_t>& outB, Count totals[2],
+                               const std::function<void(int64_t, int64_t)>& pre)
+{
+  const int64_t ntiles = (n.cap + kTile - 1) / kTile;
+  if (ntiles == 0)
+  {
+    outA.alloc(0); outB.alloc(0);
+    step_record(sites[0], 0); step_record(sites[1], 0);
+    totals[0] = Count(0); totals[1] = Count(0);
+    pre(0, 0);
+    return;
+  }
+  DevArray<int64_t> counts;
+  DevArray<int64_t> offsets(ntiles + 1);
+  const CountSource src[2] = {{offsets.p + ntiles, kCountLo32, kCountUpTo}, {offsets.p + ntiles, kCountHi32, kCountUpTo}};
+  CountPlan cp(2, sites, src);
+  const ChainState chain = fused_chain(cp.publish, ntiles);
+  CountJobs after{};
+  if (chain.state) after = cp.take_jobs();
+  else
+  {
+    counts.alloc(ntiles);
+    launch(name, compact_count2_n_kernel<TileStart, LatTileStart>, dim3((unsigned)ntiles), dim3(kBlock), 0, n, TileStart{lat.rows}, lat,
+           counts.p);
+    exclusive_scan(counts.p, offsets.p, ntiles, &cp);
+  }
+  cp.finish(totals);
+  outA.alloc(totals[0].cap()); outB.alloc(totals[1].cap());
+  if (totals[0].cell) outA.count = totals[0];
+  if (totals[1].cell) outB.count = totals[1];
+  pre(totals[0].cap(), totals[1].cap());
+  launch(name, tile_lists_write_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, n, lat, ea, eb, offsets.p, outA.p, totals[0].cap(),
+         outB.p, totals[1].cap(), chain, offsets.p + ntiles, after);
+}
+
+// LatTileStart::templ for every entry of the plain-row list (cfx_form_lattice_tile_lists: what the tests restate the
+// tile lists from)
+__global__ void __launch_bounds__(kBlock) lattice_templ_flags_kernel(DevN n_d, LatTileStart lat, uint8_t* __restrict__ out)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < dev_n(n_d)) out[i] = lat.templ(i) ? 1 : 0;
+}
+
+void lattice_tile_lists(cfx_form_s* a, int64_t* n_plain, int64_t* n_tiles, int32_t* plain_rows, uint8_t* templ,
+                        int32_t* tile_first, int32_t* tile_id)
+{
+  cfx_row_plan& plan = row_plan(a);
+  *n_plain = 0; *n_tiles = -1;
+  if (!plan.plain_masks_built || !plan.lat_tiles_built || plan.lat_bits == 0) return;
+  const int64_t np = plan.n_plain_rows.value(), nt = plan.n_lat_tiles.value();
+  *n_plain = np; *n_tiles = nt;
+  if (plain_rows && np > 0)
+  {
+    const std::vector<int32_t> r = download(plan.plain_rows.p, np);
+    std::copy(r.begin(), r.end(), plain_rows);
+  }
+  if (templ && np > 0)
+  {
+    const Stencil& S = space_lattice(a->V);
+    const LatTileStart lat{plan.plain_rows.p, plan.plain_masks.p, plan.plain_uniform.p, S.diagpos.p, (1ull << S.lat_len) - 1ull,
+                           plan.lat_bits};
+    DevArray<uint8_t> flags(np);
+    launch("lattice_templ_flags", lattice_templ_flags_kernel, grid_for(np), dim3(kBlock), 0, DevN(np), lat, flags.p);
+    const std::vector<uint8_t> f = download(flags.p, np);
+    std::copy(f.begin(), f.end(), templ);
+  }
+  if (tile_first && nt > 0)
+  {
+    const std::vector<int32_t> f = download(plan.lat_tile_first.p, nt);
+    std::copy(f.begin(), f.end(), tile_first);
+  }
+  if (tile_id && nt > 0)
+  {
+    const std::vector<int32_t> f = download(plan.lat_tile_id.p, nt);
+    std::copy(f.begin(), f.end(), tile_id);
+  }
+}
+
 bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits)
 {
   cfx_row_plan& plan = row_plan(a);
@@ -3115,7 +3284,7 @@ bool plain_row_masks(cfx_form_s* a, int32_t* counts, int* maxlen)
                                (1ull << lat->lat_len) - 1ull, lat_bits};
       const char* const sites[2] = {"plan.plain_tiles", "plan.lattice_tiles"};
       Count totals[2];
-      compact_count_pair("plan_plain_tiles", sites, plan.n_plain_rows.devn(), TileStart{plan.plain_rows.p}, lpred, emit, lemit,
+      compact_tile_lists("plan_plain_tiles", sites, plan.n_plain_rows.devn(), lpred, emit, lemit,
                          first, lfirst, totals, [&](int64_t ca, int64_t cb)
                          {
                            plan.plain_tile_id.alloc(ca); emit.ids = plan.plain_tile_id.p;

@@ -38,6 +38,7 @@
   CFX_SWITCH(VEC_ROWORDER,       first_char, call,  "0: the P1 series source term without the row-ordered staging") \
   CFX_SWITCH(SOURCE_SERIES,      first_char, call,  "0: the P1 source term by quadrature instead of its series") \
   CFX_SWITCH(SOURCE_GROUPS,      first_char, call,  "0: the P1 series source term cell by cell instead of one hex per lane") \
+  CFX_SWITCH(SOURCE_SHELL,       first_char, call,  "0: the hex kernel of the closed-form source term sifts every hex of the entity list instead of taking the shell hexes from the rows that read them; 2: shell hexes whatever the length of the list (default: from 4 M entities)") \
   CFX_SWITCH(STAGING_NAN,        first_char, call,  "1 (tests): the hex-corner planes of the staging start as NaN") \
   CFX_SWITCH(PLAIN_STAGE,        first_char, call,  "0: plain rows without LDS staging, the form that meshes with stencils longer than 32 take by themselves") \
   CFX_SWITCH(MFMA,               first_char, call,  "0: generic rows instead of the MFMA kernel for staged elasticity tensors") \

@@ -258,6 +258,20 @@ class CutForm:
         _lib.check(_lib.lib().cfx_form_prepare(self._h))
         return self
 
+    def lattice_tile_lists(self):
+        """Diagnostics (cfx_form_lattice_tile_lists): None, or the plan's plain rows, their template flags and the
+        filtered tile list as a dict of numpy arrays (plain_rows, templ, tile_first, tile_id)."""
+        n, t = C.c_int64(0), C.c_int64(-1)
+        f = _lib.lib().cfx_form_lattice_tile_lists
+        _lib.check(f(self._h, C.byref(n), C.byref(t), None, None, None, None))
+        if t.value < 0:
+            return None
+        rows, templ = np.zeros(max(n.value, 1), dtype=np.int32), np.zeros(max(n.value, 1), dtype=np.uint8)
+        first, ids = np.zeros(max(t.value, 1), dtype=np.int32), np.zeros(max(t.value, 1), dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        _lib.check(f(self._h, C.byref(n), C.byref(t), ptr(rows), ptr(templ), ptr(first), ptr(ids)))
+        return dict(plain_rows=rows[:n.value], templ=templ[:n.value], tile_first=first[:t.value], tile_id=ids[:t.value])
+
     def __del__(self):
         try:
             if self._h:

@@ -418,6 +418,11 @@ int cfx_space_lattice_rows(cfx_space_t V, int64_t* n, int64_t* template_rows);
  * mesh-static moments of the representative row's cells times sin / cos of the row's own coordinates; the result
  * differs from the cell loop's by rounding only.  0 without lattice rows, in 2-D, under CFX_LATTICE_SOURCE=0. */
 int cfx_space_lattice_source_rows(cfx_space_t V, int64_t* rows);
+/* Hexes (cells 6h .. 6h+5 of a mesh of hex groups) the hex kernel of the series source term ran in the last assembly of
+ * a linear form on this space, when it took them from the rows that read them: the hexes with a tet that is an entity
+ * of the integral and has a corner row that does not take the closed form above.  0 when the last assembly did not go
+ * that way (no lattice rows, CFX_LATTICE_SOURCE=0, CFX_SOURCE_SHELL=0).  Diagnostics (tests: "path taken"). */
+int cfx_space_source_shell_hexes(cfx_space_t V, int64_t* hexes);
 int cfx_space_destroy(cfx_space_t V);
 
 /* ---- forms: dolfinx_custom_data::fem::Form, Form.h:119-178, built as in
@@ -440,6 +445,12 @@ int cfx_form_destroy(cfx_form_t a);
 /* build the form's derived tables now (row plan: cell / row marks, row classes, rule maps, facet incidence, stencil
  * masks, the row-ordered staging layout of a linear form) instead of inside the first assembly call that needs them */
 int cfx_form_prepare(cfx_form_t a);
+/* Diagnostics (tests): the filtered tile list of a bilinear form on a space with lattice rows, as its plan holds it
+ * after a sparsity build or an assembly: host arrays plain_rows[n_plain], templ[n_plain] (1: the row is copied from
+ * the lattice template), tile_first[n_tiles] (position in plain_rows of the first row of its 16-row tile that is not
+ * such a row) and tile_id[n_tiles].  Null arrays are skipped: call once for the sizes.  n_tiles = -1: no such list. */
+int cfx_form_lattice_tile_lists(cfx_form_t a, int64_t* n_plain, int64_t* n_tiles, int32_t* plain_rows, uint8_t* templ,
+                                int32_t* tile_first, int32_t* tile_id);
 /* create_sparsity_pattern(): assembler.h:567-592 (+ :442-529, :538-560) */
 int cfx_create_sparsity(cfx_form_t a, cfx_pattern_t* out);
 int cfx_pattern_view_get(cfx_pattern_t p, cfx_pattern_view* view);
