@@ -1,4 +1,5 @@
-// cutfemx_amd: the solve of assembled CSR systems in HBM -- y = A x and Jacobi-preconditioned conjugate gradients.
+// cutfemx_amd: the solve of assembled CSR systems in HBM -- y = A x, Jacobi-preconditioned conjugate gradients and
+// diagonally preconditioned MINRES.
 //
 // Replaces the host solve of the reference's demos (python/demo/demo_poisson.py:46-58, demo_moving_poisson.py:53-67:
 // PETSc KSP on the assembled matrix) for the symmetric positive definite systems cfx_assemble_matrix +
@@ -35,6 +36,22 @@
 // and block 0 writes slot (l + 1) & 1; rho of iteration `it` lives in slot it & 1.  Once the state leaves "running" every
 // later launch returns at once, so x and the iteration count are frozen at the converged iterate and the result does
 // not depend on how often the host looks (check_every); with check_every = 0 and a device `info` the host never looks.
+//
+// MINRES (cfx_minres_solve) replaces the direct solve of the reference's Stokes demo (python/demo/demo_stokes.py:39-60)
+// for SYMMETRIC, possibly indefinite matrices -- the saddle-point systems of merged Stokes blocks.  It obeys every rule
+// above.  Paige-Saunders MINRES in the Lanczos form with an SPD diagonal M (|a_ii|, sum_j |a_ij| or 1):
+//   v: Lanczos vectors (v_j with |v_j|_{M^-1} = gamma_j), z = M^-1 v_j / gamma_j, w: search directions
+//   by list position: v, v_old, q, w, w_old, 1/m;  by row: z (read through the column indices, 0 outside the list), x
+// One iteration = three launches:
+//   minres_spmv     q = A z, partials of z.q = delta                 (solve_spmv_kernel<kCg> with z in p's place)
+//   minres_lanczos  v_new = q - (delta / gamma1) v - (gamma1 / gamma0) v_old over v_old; partials of v_new . M^-1 v_new
+//   minres_update   gamma2 = sqrt of that sum; the rotations; w_new = (z - a3 w_old - a2 w) / a1 over w_old;
+//                   x += c eta w_new; z = M^-1 v_new / gamma2; eta' = -s eta; the stopping test on |eta'| = |r|_{M^-1}
+// (the host swaps v / v_old and w / w_old by iteration parity).  Set-up: minres_init (the row pass: r0 = b - A x0, 1/m,
+// z = M^-1 r0, partials of r0 . M^-1 r0 and b . M^-1 b), minres_start (one block: gamma1, the threshold, the state) and
+// minres_normalise (z /= gamma1, once).  MinresRecord continues CgRecord: the scalars of the recurrence -- gamma_k,
+// gamma_{k+1}, c and s of the last two rotations, eta -- live in two slots, iteration `it` reads slot it & 1 and block 0
+// of minres_update writes slot (it + 1) & 1; delta goes from minres_lanczos to minres_update through delta[it & 1].
 #include "cfx_device.h"
 
 using namespace cfx;
@@ -43,7 +60,7 @@ namespace
 {
 constexpr int kMaxGrid = 2048; // blocks of every solve kernel (8 waves per SIMD on 256 CUs); slabs of 16 KB
 constexpr int kRunning = 0;    // state word; every other value is the cfx_cg_info::reason
-enum { kPlain = 0, kInit = 1, kCg = 2 };
+enum { kPlain = 0, kInit = 1, kCg = 2, kMinresInit = 3 };
 
 struct CgRecord
 {
@@ -54,6 +71,20 @@ struct CgRecord
   unsigned long long nnz; // stored entries of the iterated rows (solve_count_kernel)
   int32_t bad_diagonal;   // set by cg_init: a listed row without a stored diagonal, or with a zero one
   int32_t reserved;
+};
+
+struct MinresScalars
+{
+  double gamma0, gamma1; // |v_{k-1}|, |v_k| in the M^-1 norm (gamma0 = 1 before the first iteration)
+  double c0, s0, c1, s1; // the last two rotations
+  double eta;            // |eta| = |r|_{M^-1}
+  double reserved;
+};
+
+struct MinresRecord : CgRecord // (the kernels shared with CG see the CgRecord)
+{
+  MinresScalars sc[2]; // iteration it reads [it & 1]; block 0 of minres_update writes [(it + 1) & 1]
+  double delta[2];     // z.Az of iteration it in [it & 1]: minres_lanczos -> minres_update
 };
 
 struct SolveArgs
@@ -77,6 +108,13 @@ struct SolveArgs
   double* slab0;       // partials: kInit r.z, kCg p.q, cg_update r.z
   double* slab1;       //           kInit r.r,          cg_update r.r
   double* slab2;       //           kInit b.b
+  // MINRES (v, v_old, q, w, w_old, dinv = 1 / m by list position; p = z by row)
+  double* v;           // r is not used
+  double* v_old;       // minres_lanczos writes v_new here
+  double* w;
+  double* w_old;       // minres_update writes w_new here
+  MinresRecord* mrec;  // == rec
+  int pc;              // kMinresInit: CFX_PC_NONE, CFX_PC_ABS_JACOBI or CFX_PC_ABS_ROWSUM
   int nslab;           // partials the PREVIOUS kernel of the chain wrote
   int it;              // iteration (0-based)
   int launch;          // 3 it + {0, 1, 2}
@@ -189,6 +227,13 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
         {
           s[u] += v[u] * xv[u];
           if (MODE == kInit && c[u] == row[u]) d[u] += v[u];
+          if (MODE == kMinresInit)
+          {
+            if (S.pc == CFX_PC_ABS_ROWSUM)
+              d[u] += fabs(v[u]);
+            else if (c[u] == row[u])
+              d[u] += v[u];
+          }
           j[u] += L;
         }
         more = more || j[u] < j1[u];
@@ -201,7 +246,7 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
       for (int o = L / 2; o > 0; o >>= 1)
       {
         s[u] += __shfl_down(s[u], o, L);
-        if (MODE == kInit) d[u] += __shfl_down(d[u], o, L);
+        if (MODE == kInit || MODE == kMinresInit) d[u] += __shfl_down(d[u], o, L);
       }
     }
 #pragma unroll
@@ -214,6 +259,26 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
       {
         S.q[k[u]] = s[u];
         acc[0] += S.x[row[u]] * s[u];
+      }
+      else if (MODE == kMinresInit)
+      {
+        const double bk = S.b[row[u]], rk = bk - s[u];
+        double mi = 1.0;
+        if (S.dinv)
+        {
+          const double m = fabs(d[u]);
+          if (!(m > 0.0)) S.rec->bad_diagonal = 1; // (every writer stores the same value)
+          mi = 1.0 / m;
+          S.dinv[k[u]] = mi;
+        }
+        const double z = rk * mi;
+        S.v[k[u]] = rk;
+        S.v_old[k[u]] = 0.0;
+        S.w[k[u]] = 0.0;
+        S.w_old[k[u]] = 0.0;
+        S.p[row[u]] = z;
+        acc[0] += rk * z;
+        acc[1] += bk * (bk * mi);
       }
       else
       {
@@ -237,7 +302,8 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
 }
 
 // kPlain: y[rows] = (A x)[rows].  kInit: r = b - A x0, 1/diag, z = r / diag, p = z, partials of r.z, r.r, b.b.
-// kCg: q = A p, partials of p.q.
+// kCg: q = A p, partials of p.q.  kMinresInit: r0 = b - A x0 into v, 1/m, z = M^-1 r0 into p, v_old = w = w_old = 0,
+// partials of r0 . M^-1 r0 and b . M^-1 b.
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) solve_spmv_kernel(SolveArgs S)
 {
@@ -256,6 +322,11 @@ __global__ void __launch_bounds__(kBlock) solve_spmv_kernel(SolveArgs S)
   if (MODE == kPlain) return;
   const double s0 = block_sum_all(acc[0], wave_sums);
   if (threadIdx.x == 0) S.slab0[blockIdx.x] = s0;
+  if (MODE == kMinresInit)
+  {
+    const double s1 = block_sum_all(acc[1], wave_sums);
+    if (threadIdx.x == 0) S.slab1[blockIdx.x] = s1;
+  }
   if (MODE == kInit)
   {
     const double s1 = block_sum_all(acc[1], wave_sums), s2 = block_sum_all(acc[2], wave_sums);
@@ -379,6 +450,153 @@ __global__ void __launch_bounds__(kBlock) cg_direction_kernel(SolveArgs S)
       const double rk = S.r[k];
       const double z = S.dinv ? rk * S.dinv[k] : rk;
       S.p[row] = z + beta * S.p[row];
+    }
+  }
+}
+
+// ---- MINRES ---------------------------------------------------------------------------------------------------------
+// ONE block, after minres_init: gamma1 = |r0|_{M^-1}, |b|_{M^-1}, the threshold, the scalars of iteration 0 and the state
+// the first launch reads
+__global__ void __launch_bounds__(kBlock) minres_start_kernel(SolveArgs S, double rtol, double atol, int max_iter)
+{
+  __shared__ double wave_sums[kBlock / 64];
+  const double rz = slab_sum(S.slab0, S.nslab, wave_sums), bb = slab_sum(S.slab1, S.nslab, wave_sums);
+  if (threadIdx.x != 0) return;
+  MinresRecord& R = *S.mrec;
+  const double bnorm = sqrt(bb), rnorm = sqrt(rz), threshold = fmax(rtol * bnorm, atol);
+  int st = kRunning;
+  if (S.dinv && R.bad_diagonal)
+    st = CFX_CG_BAD_DIAGONAL;
+  else if (!isfinite(rz))
+    st = CFX_CG_BREAKDOWN;
+  else if (rnorm <= threshold)
+    st = CFX_CG_CONVERGED;
+  else if (max_iter == 0)
+    st = CFX_CG_MAX_ITER;
+  R.info.reason = st;
+  R.info.iterations = 0;
+  R.info.residual_norm = rnorm;
+  R.info.rhs_norm = bnorm;
+  R.threshold = threshold;
+  MinresScalars& sc = R.sc[0];
+  sc.gamma0 = 1.0;
+  sc.gamma1 = rnorm;
+  sc.c0 = sc.c1 = 1.0;
+  sc.s0 = sc.s1 = 0.0;
+  sc.eta = rnorm;
+  R.state[0] = st;
+}
+
+// z = M^-1 r0 / gamma1 (once, launch 0)
+__global__ void __launch_bounds__(kBlock) minres_normalise_kernel(SolveArgs S)
+{
+  if (state_in(S) != kRunning) return;
+  const double zs = 1.0 / S.mrec->sc[0].gamma1;
+  const int64_t tiles = (S.n + kBlock - 1) / kBlock;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x)
+  {
+    const int64_t k = t * kBlock + threadIdx.x;
+    if (k < S.n)
+    {
+      const int64_t row = S.rows ? (int64_t)S.rows[k] : k;
+      S.p[row] *= zs;
+    }
+  }
+}
+
+// delta = z.q;  v_new = q - (delta / gamma1) v - (gamma1 / gamma0) v_old, over v_old;  partials of v_new . M^-1 v_new
+__global__ void __launch_bounds__(kBlock) minres_lanczos_kernel(SolveArgs S)
+{
+  __shared__ double wave_sums[kBlock / 64];
+  if (state_in(S) != kRunning) return;
+  const double delta = slab_sum(S.slab0, S.nslab, wave_sums);
+  const bool breakdown = !isfinite(delta);
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    S.mrec->state[(S.launch + 1) & 1] = breakdown ? CFX_CG_BREAKDOWN : kRunning;
+    if (breakdown) S.mrec->info.reason = CFX_CG_BREAKDOWN;
+    S.mrec->delta[S.it & 1] = delta;
+  }
+  if (breakdown) return;
+  const MinresScalars& sc = S.mrec->sc[S.it & 1];
+  const double a = delta / sc.gamma1, bcoef = sc.gamma1 / sc.gamma0;
+  double acc = 0.0;
+  const int64_t tiles = (S.n + kBlock - 1) / kBlock;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x)
+  {
+    const int64_t k = t * kBlock + threadIdx.x;
+    if (k < S.n)
+    {
+      const double vn = S.q[k] - a * S.v[k] - bcoef * S.v_old[k];
+      S.v_old[k] = vn;
+      acc += vn * (S.dinv ? vn * S.dinv[k] : vn);
+    }
+  }
+  const double s0 = block_sum_all(acc, wave_sums);
+  if (threadIdx.x == 0) S.slab1[blockIdx.x] = s0; // (slab0 holds z.q, which other blocks of this launch may still be reading)
+}
+
+// gamma2, the rotations, w_new over w_old, x += c eta w_new, z = M^-1 v_new / gamma2, the stopping test.  S.v_old is the
+// v_new minres_lanczos wrote.
+__global__ void __launch_bounds__(kBlock) minres_update_kernel(SolveArgs S)
+{
+  __shared__ double wave_sums[kBlock / 64];
+  if (state_in(S) != kRunning) return;
+  const double g2sq = slab_sum(S.slab1, S.nslab, wave_sums);
+  MinresRecord& R = *S.mrec;
+  const MinresScalars sc = R.sc[S.it & 1];
+  const double delta = R.delta[S.it & 1];
+  const double gamma2 = sqrt(g2sq);
+  // every block computes the same rotations
+  const double a0 = sc.c1 * delta - sc.c0 * sc.s1 * sc.gamma1;
+  const double a1 = sqrt(a0 * a0 + g2sq);
+  const double a2 = sc.s1 * delta + sc.c0 * sc.c1 * sc.gamma1;
+  const double a3 = sc.s0 * sc.gamma1;
+  const bool breakdown = !isfinite(g2sq) || !(a1 > 0.0) || !isfinite(a1); // (no update of x)
+  if (breakdown)
+  {
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+    {
+      R.state[(S.launch + 1) & 1] = CFX_CG_BREAKDOWN;
+      R.info.reason = CFX_CG_BREAKDOWN;
+    }
+    return;
+  }
+  const double c2 = a0 / a1, s2 = gamma2 / a1;
+  const double eta2 = -s2 * sc.eta, rnorm = fabs(eta2);
+  // gamma2 == 0: the Krylov space is exhausted -- the update is finished, then the rule decides
+  const int st = rnorm <= R.threshold ? CFX_CG_CONVERGED
+                 : !(gamma2 > 0.0)    ? CFX_CG_BREAKDOWN
+                 : S.last             ? CFX_CG_MAX_ITER
+                                      : kRunning;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    MinresScalars& out = R.sc[(S.it + 1) & 1];
+    out.gamma0 = sc.gamma1;
+    out.gamma1 = gamma2;
+    out.c0 = sc.c1;
+    out.s0 = sc.s1;
+    out.c1 = c2;
+    out.s1 = s2;
+    out.eta = eta2;
+    R.info.iterations = S.it + 1;
+    R.info.residual_norm = rnorm;
+    if (st != kRunning) R.info.reason = st;
+    R.state[(S.launch + 1) & 1] = st;
+  }
+  const double step = c2 * sc.eta, zs = gamma2 > 0.0 ? 1.0 / gamma2 : 0.0;
+  const int64_t tiles = (S.n + kBlock - 1) / kBlock;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x)
+  {
+    const int64_t k = t * kBlock + threadIdx.x;
+    if (k < S.n)
+    {
+      const int64_t row = S.rows ? (int64_t)S.rows[k] : k;
+      const double wn = (S.p[row] - a3 * S.w_old[k] - a2 * S.w[k]) / a1;
+      S.w_old[k] = wn;
+      S.xs[row] += step * wn;
+      const double vn = S.v_old[k];
+      S.p[row] = (S.dinv ? vn * S.dinv[k] : vn) * zs;
     }
   }
 }
@@ -519,6 +737,96 @@ int cfx_cg_solve(int64_t nrows, const int64_t* indptr, const int32_t* indices, c
     S.launch = 3 * it + 2;
     S.nslab = g_vec;
     launch("cg_direction", cg_direction_kernel, dim3(g_vec), dim3(kBlock), 0, S);
+    // the host looks every check_every iterations; what it sees only ends the launches (the result is frozen in HBM)
+    if (o.check_every > 0 && (it + 1) % o.check_every == 0 && !S.last && read_scalar(&rec.p->info.reason) != kRunning) break;
+  }
+  if (is_device_pointer(info))
+    CFX_HIP(hipMemcpyAsync(info, &rec.p->info, sizeof(cfx_cg_info), hipMemcpyDeviceToDevice, ctx().stream));
+  else
+    *info = read_scalar(&rec.p->info);
+  xo.finish();
+  CFX_API_END
+}
+
+int cfx_minres_options_default(cfx_minres_options* opt)
+{
+  CFX_API_BEGIN
+  require(opt != nullptr, CFX_ERR_INVALID_ARGUMENT, "cfx_minres_options_default: null argument");
+  opt->rtol = 1e-10;
+  opt->atol = 0.0;
+  opt->max_iter = 10000;
+  opt->check_every = 16;
+  opt->precond = CFX_PC_ABS_JACOBI;
+  opt->lanes_per_row = 0;
+  CFX_API_END
+}
+
+int cfx_minres_solve(int64_t nrows, const int64_t* indptr, const int32_t* indices, const double* values, const int32_t* rows,
+                     int64_t n_rows, const double* b, double* x, const cfx_minres_options* opt, cfx_cg_info* info)
+{
+  CFX_API_BEGIN
+  cfx_minres_options o;
+  if (opt)
+    o = *opt;
+  else
+    cfx_minres_options_default(&o);
+  check_csr("cfx_minres_solve", nrows, indptr, indices, values, rows, n_rows, o.lanes_per_row);
+  require(b && x && info, CFX_ERR_INVALID_ARGUMENT, "cfx_minres_solve: null b, x or info");
+  require(o.rtol >= 0.0 && o.atol >= 0.0, CFX_ERR_INVALID_ARGUMENT, "cfx_minres_solve: rtol and atol are >= 0");
+  require(o.max_iter >= 0 && o.check_every >= 0, CFX_ERR_INVALID_ARGUMENT, "cfx_minres_solve: max_iter and check_every are >= 0");
+  require(o.max_iter <= 0x2aaaaaaa, CFX_ERR_INVALID_ARGUMENT, "cfx_minres_solve: max_iter too large");
+  require(o.precond == CFX_PC_NONE || o.precond == CFX_PC_ABS_JACOBI || o.precond == CFX_PC_ABS_ROWSUM, CFX_ERR_INVALID_ARGUMENT,
+          "cfx_minres_solve: precond is CFX_PC_NONE, CFX_PC_ABS_JACOBI or CFX_PC_ABS_ROWSUM");
+  ctx().ensure();
+  for (const void* p : {(const void*)indptr, (const void*)indices, (const void*)values})
+    require_device("cfx_minres_solve", p, "the CSR arrays");
+  if (rows) require_device("cfx_minres_solve", rows, "rows");
+
+  const int64_t n = rows ? n_rows : nrows;
+  const bool pc = o.precond != CFX_PC_NONE;
+  DevArray<double> bd = to_device(b, nrows);
+  OutArray<double> xo(x, nrows, true);
+  // workspace from the block cache: v, v_old, q, w, w_old, 1/m by list position, z by row, two slabs, the record
+  DevArray<double> va(n), vb(n), q(n), wa(n), wb(n), minv(pc ? n : 0), z(nrows), slabs(2 * (int64_t)kMaxGrid);
+  DevArray<MinresRecord> rec(1);
+  rec.zero();
+  if (rows) z.zero(); // z stays 0 outside the list
+
+  SolveArgs S{};
+  S.indptr = indptr; S.indices = indices; S.values = values; S.rows = rows;
+  S.n = n;
+  S.lanes = o.lanes_per_row;
+  S.rec = rec.p; S.mrec = rec.p;
+  S.pc = o.precond;
+  S.b = bd.p; S.xs = xo.dev; S.p = z.p; S.q = q.p;
+  S.v = va.p; S.v_old = vb.p; S.w = wa.p; S.w_old = wb.p;
+  S.dinv = pc ? minv.p : nullptr;
+  S.slab0 = slabs.p; S.slab1 = slabs.p + kMaxGrid;
+  if (S.lanes == 0) count_entries(S, nrows);
+
+  const int g_rows = spmv_blocks(n), g_vec = grid_blocks(n, kBlock);
+  S.x = xo.dev;
+  launch("minres_init", solve_spmv_kernel<kMinresInit>, dim3(g_rows), dim3(kBlock), 0, S);
+  S.nslab = g_rows;
+  launch("minres_start", minres_start_kernel, dim3(1), dim3(kBlock), 0, S, o.rtol, o.atol, (int)o.max_iter);
+  S.launch = 0;
+  launch("minres_normalise", minres_normalise_kernel, dim3(g_vec), dim3(kBlock), 0, S);
+
+  S.x = z.p;
+  for (int it = 0; it < o.max_iter; ++it)
+  {
+    S.it = it;
+    S.last = it + 1 == o.max_iter;
+    S.v = it & 1 ? vb.p : va.p; S.v_old = it & 1 ? va.p : vb.p;
+    S.w = it & 1 ? wb.p : wa.p; S.w_old = it & 1 ? wa.p : wb.p;
+    S.launch = 3 * it + 1;
+    launch("minres_spmv", solve_spmv_kernel<kCg>, dim3(g_rows), dim3(kBlock), 0, S);
+    S.launch = 3 * it + 2;
+    S.nslab = g_rows;
+    launch("minres_lanczos", minres_lanczos_kernel, dim3(g_vec), dim3(kBlock), 0, S);
+    S.launch = 3 * it + 3;
+    S.nslab = g_vec;
+    launch("minres_update", minres_update_kernel, dim3(g_vec), dim3(kBlock), 0, S);
     // the host looks every check_every iterations; what it sees only ends the launches (the result is frozen in HBM)
     if (o.check_every > 0 && (it + 1) % o.check_every == 0 && !S.last && read_scalar(&rec.p->info.reason) != kRunning) break;
   }

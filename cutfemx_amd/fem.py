@@ -739,8 +739,9 @@ def assemble_scalar(M: CutForm, out=None):
     return complex(b.sum()) if _is_complex(M.dtype) else float(b.sum())
 
 
-# ---- the solve in HBM: y = A x and Jacobi-preconditioned CG (cfx_csr_spmv / cfx_cg_solve) ----------------------------
+# ---- the solve in HBM: y = A x, Jacobi-preconditioned CG and MINRES (cfx_csr_spmv / cfx_cg_solve / cfx_minres_solve) ----
 PC_NONE, PC_JACOBI = _lib.PC_NONE, _lib.PC_JACOBI
+PC_ABS_JACOBI, PC_ABS_ROWSUM = _lib.PC_ABS_JACOBI, _lib.PC_ABS_ROWSUM   # minres_solve alone
 CG_CONVERGED, CG_MAX_ITER, CG_BREAKDOWN, CG_BAD_DIAGONAL = (_lib.CG_CONVERGED, _lib.CG_MAX_ITER, _lib.CG_BREAKDOWN,
                                                            _lib.CG_BAD_DIAGONAL)
 _CG_REASONS = {CG_CONVERGED: "converged", CG_MAX_ITER: "max_iter", CG_BREAKDOWN: "breakdown",
@@ -750,7 +751,7 @@ _CG_REASONS = {CG_CONVERGED: "converged", CG_MAX_ITER: "max_iter", CG_BREAKDOWN:
 @dataclass
 class CGInfo:
     """cfx_cg_info: why cg_solve stopped, after how many updates of x, |r|_2 of the recurrence and |b|_2 (both over
-    the iterated rows)."""
+    the iterated rows).  minres_solve returns the same record with the two norms taken in the M^-1 norm of its rule."""
     reason: int
     iterations: int
     residual_norm: float
@@ -896,6 +897,60 @@ def spmv(A, x, out=None, rows=None, lanes_per_row: int = 0):
     return out
 
 
+def _krylov_solve(who: str, entry: str, o, A, b, x0, rows, domain, info_out):
+    """The call both solvers make (cfx_cg_solve / cfx_minres_solve have one argument list): vectors, row list and info
+    of `who`, then `entry` with the options `o`; returns (x, info)."""
+    nrows, ip, ix, va = _csr_arrays(A)
+    keep: list = []
+    if domain is not None:
+        rows = active_rows(domain)
+    rp, nr = _row_list(rows, keep)
+    if _lib.is_torch(b) and b.is_cuda:
+        import torch
+        if b.dtype != torch.float64 or not b.is_contiguous() or b.numel() != nrows:
+            raise TypeError(f"b must be a contiguous float64 tensor of {nrows} values")
+        x = torch.zeros_like(b) if x0 is None else torch.as_tensor(x0, dtype=torch.float64, device=b.device).clone().contiguous()
+        bp, xp = C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr())
+    else:
+        if _lib.is_device(b) or _lib.is_device(x0):
+            raise TypeError(f"{who}: b (and x0) are numpy arrays or device torch tensors")
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.zeros(nrows) if x0 is None else np.array(x0, dtype=np.float64).ravel()
+        bp, xp = b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p)
+        if b.size != nrows:
+            raise ValueError(f"b must hold {nrows} values")
+    if (x.numel() if _lib.is_torch(x) else x.size) != nrows:
+        raise ValueError(f"x0 must hold {nrows} values")
+    fn = getattr(_lib.lib(), entry)
+    if info_out is not None:
+        if not _lib.is_device(info_out):
+            raise TypeError(f"{who}: info_out is a device buffer (cg_info_buffer())")
+        ipn = _device_f64(info_out, 3, "info_out", keep)
+        _lib.check(fn(C.c_int64(nrows), C.c_void_p(ip), C.c_void_p(ix), C.c_void_p(va), rp, C.c_int64(nr), bp, xp, C.byref(o), ipn))
+        return x, info_out
+    st = _lib.CGInfoStruct()
+    _lib.check(fn(C.c_int64(nrows), C.c_void_p(ip), C.c_void_p(ix), C.c_void_p(va), rp, C.c_int64(nr), bp, xp, C.byref(o),
+                  C.byref(st)))
+    return x, CGInfo(int(st.reason), int(st.iterations), float(st.residual_norm), float(st.rhs_norm))
+
+
+def _krylov_options(who: str, o, A, rows, domain, names: dict, precond, rtol, atol, max_iter, check_every, lanes_per_row):
+    """The checks that run before the library is entered, and the options struct filled from the keywords."""
+    if A.ncols != A.nrows:
+        raise ValueError(f"{who} takes a square matrix")
+    if rows is not None and domain is not None:
+        raise ValueError(f"{who}: give `rows` or `domain`, not both")
+    pc = names.get(precond.lower() if isinstance(precond, str) else precond)
+    if pc is None:
+        raise ValueError(f"{who}: precond is " + " or ".join(repr(k) for k in names if isinstance(k, str)))
+    o.rtol, o.atol, o.precond, o.lanes_per_row = float(rtol), float(atol), pc, int(lanes_per_row)
+    if max_iter is not None:
+        o.max_iter = int(max_iter)
+    if check_every is not None:
+        o.check_every = int(check_every)
+    return o
+
+
 def cg_solve(A, b, x0=None, *, rtol: float = 1e-10, atol: float = 0.0, max_iter: int | None = None,
              precond: str = "jacobi", rows=None, domain=None, check_every: int | None = None, info_out=None,
              lanes_per_row: int = 0):
@@ -909,52 +964,35 @@ def cg_solve(A, b, x0=None, *, rtol: float = 1e-10, atol: float = 0.0, max_iter:
     `info_out` (cg_info_buffer()): the cfx_cg_info stays in HBM, `info` is then info_out itself and -- with device
     vectors and check_every = 0 -- the call makes no host round trip: exactly `max_iter` iterations are launched and the
     ones after convergence return at once."""
-    nrows, ip, ix, va = _csr_arrays(A)
-    if A.ncols != nrows:
-        raise ValueError("cg_solve takes a square matrix")
-    if rows is not None and domain is not None:
-        raise ValueError("cg_solve: give `rows` or `domain`, not both")
-    pc = {"jacobi": PC_JACOBI, "none": PC_NONE, None: PC_NONE}.get(precond.lower() if isinstance(precond, str) else precond)
-    if pc is None:
-        raise ValueError("cg_solve: precond is 'jacobi' or 'none'")
-    o = cg_default_options()
-    o.rtol, o.atol, o.precond, o.lanes_per_row = float(rtol), float(atol), pc, int(lanes_per_row)
-    if max_iter is not None:
-        o.max_iter = int(max_iter)
-    if check_every is not None:
-        o.check_every = int(check_every)
-    keep: list = []
-    if domain is not None:
-        rows = active_rows(domain)
-    rp, nr = _row_list(rows, keep)
-    if _lib.is_torch(b) and b.is_cuda:
-        import torch
-        if b.dtype != torch.float64 or not b.is_contiguous() or b.numel() != nrows:
-            raise TypeError(f"b must be a contiguous float64 tensor of {nrows} values")
-        x = torch.zeros_like(b) if x0 is None else torch.as_tensor(x0, dtype=torch.float64, device=b.device).clone().contiguous()
-        bp, xp = C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr())
-    else:
-        if _lib.is_device(b) or _lib.is_device(x0):
-            raise TypeError("cg_solve: b (and x0) are numpy arrays or device torch tensors")
-        b = np.ascontiguousarray(b, dtype=np.float64)
-        x = np.zeros(nrows) if x0 is None else np.array(x0, dtype=np.float64).ravel()
-        bp, xp = b.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p)
-        if b.size != nrows:
-            raise ValueError(f"b must hold {nrows} values")
-    if (x.numel() if _lib.is_torch(x) else x.size) != nrows:
-        raise ValueError(f"x0 must hold {nrows} values")
-    l = _lib.lib()
-    if info_out is not None:
-        if not _lib.is_device(info_out):
-            raise TypeError("cg_solve: info_out is a device buffer (cg_info_buffer())")
-        ipn = _device_f64(info_out, 3, "info_out", keep)
-        _lib.check(l.cfx_cg_solve(C.c_int64(nrows), C.c_void_p(ip), C.c_void_p(ix), C.c_void_p(va), rp, C.c_int64(nr), bp, xp,
-                                  C.byref(o), ipn))
-        return x, info_out
-    st = _lib.CGInfoStruct()
-    _lib.check(l.cfx_cg_solve(C.c_int64(nrows), C.c_void_p(ip), C.c_void_p(ix), C.c_void_p(va), rp, C.c_int64(nr), bp, xp,
-                              C.byref(o), C.byref(st)))
-    return x, CGInfo(int(st.reason), int(st.iterations), float(st.residual_norm), float(st.rhs_norm))
+    _csr_arrays(A)
+    o = _krylov_options("cg_solve", cg_default_options(), A, rows, domain, {"jacobi": PC_JACOBI, "none": PC_NONE, None: PC_NONE},
+                        precond, rtol, atol, max_iter, check_every, lanes_per_row)
+    return _krylov_solve("cg_solve", "cfx_cg_solve", o, A, b, x0, rows, domain, info_out)
+
+
+def minres_default_options() -> _lib.CGOptions:
+    """The defaults of cfx_minres_options_default (no GPU needed)."""
+    o = _lib.CGOptions()
+    _lib.check(_lib.load().cfx_minres_options_default(C.byref(o)))
+    return o
+
+
+def minres_solve(A, b, x0=None, *, rtol: float = 1e-10, atol: float = 0.0, max_iter: int | None = None,
+                 check_every: int | None = None, precond: str | None = "abs_jacobi", rows=None, domain=None,
+                 lanes_per_row: int = 0, info_out=None):
+    """Solve A x = b for a SYMMETRIC, possibly indefinite A by diagonally preconditioned MINRES in HBM
+    (cfx_minres_solve); returns (x, info) -- what python/demo/demo_stokes.py:39-60 leaves to spsolve.
+
+    Arguments, row-list semantics and return value are those of cg_solve (`A`: MatrixCSR, MergedCSR or csr_from_arrays).
+    Symmetry on the iterated rows is required and NOT checked.  precond: "abs_jacobi" (m_i = |a_ii|; a listed row
+    without a nonzero stored diagonal gives reason CG_BAD_DIAGONAL), "abs_rowsum" (m_i = sum_j |a_ij|: works where the
+    diagonal is absent) or None / "none".  Stops at |r|_{M^-1} <= max(rtol |b|_{M^-1}, atol), |y|_{M^-1} = sqrt(y . M^-1 y)
+    over the iterated rows; info.residual_norm / rhs_norm are these norms (the 2-norms when there is no preconditioner)."""
+    _csr_arrays(A)
+    names = {"abs_jacobi": PC_ABS_JACOBI, "abs_rowsum": PC_ABS_ROWSUM, "none": PC_NONE, None: PC_NONE}
+    o = _krylov_options("minres_solve", minres_default_options(), A, rows, domain, names, precond, rtol, atol, max_iter,
+                        check_every, lanes_per_row)
+    return _krylov_solve("minres_solve", "cfx_minres_solve", o, A, b, x0, rows, domain, info_out)
 
 
 def zero_rows(A: MatrixCSR, *, tol: float = 0.0) -> np.ndarray:

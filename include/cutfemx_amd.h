@@ -704,6 +704,39 @@ int cfx_cg_solve(int64_t nrows, const int64_t* indptr, const int32_t* indices, c
                  const int32_t* rows, int64_t n_rows, const double* b, double* x /* in: x0, out: x */,
                  const cfx_cg_options* opt /* or NULL: the defaults */, cfx_cg_info* info /* host or device pointer */);
 
+/* ---- the solve of symmetric INDEFINITE systems: diagonally preconditioned MINRES ----------------------------------
+ * What the reference's Stokes demo hands to a direct solver after assembly (python/demo/demo_stokes.py:39-60: spsolve
+ * of the monolithic matrix): the saddle-point matrix of cfx_csr_block_merge after the deactivation of its diagonal
+ * blocks, solved in HBM.  Paige-Saunders MINRES (the Lanczos form) with an SPD diagonal preconditioner M.  The matrix
+ * MUST be symmetric on the iterated rows (A[rows, rows] symmetric); this is NOT checked -- on a non-symmetric matrix
+ * the call returns some x and reports what the recurrence says.  It need not be definite.
+ *
+ * The arguments, the row list, lanes_per_row, check_every, the host / device rules for b, x and info, and the fixed
+ * order of every sum are those of cfx_cg_solve; cfx_cg_info and the CFX_CG_* reasons are reused.  Preconditioners
+ * (cfx_cg_solve refuses the two new ids):
+ *   CFX_PC_NONE        M = I
+ *   CFX_PC_ABS_JACOBI  m_i = |a_ii|; a listed row without a stored diagonal entry, or with a zero one, gives
+ *                      CFX_CG_BAD_DIAGONAL and x = x0
+ *   CFX_PC_ABS_ROWSUM  m_i = sum_j |a_ij| over the row's stored entries: works where the diagonal is absent (the
+ *                      pressure rows of an unstabilised pair); an empty (or all-zero) listed row gives
+ *                      CFX_CG_BAD_DIAGONAL
+ * Stopping rule: |r|_{M^-1} <= max(rtol |b|_{M^-1}, atol) with |y|_{M^-1} = sqrt(y . M^-1 y) over the iterated rows --
+ * the quantity MINRES minimises and carries for free (|eta| of the recurrence); with CFX_PC_NONE it is the 2-norm of
+ * cfx_cg_solve's rule.  residual_norm / rhs_norm of the info hold these two norms.
+ *   CFX_CG_CONVERGED     as for cfx_cg_solve (0 iterations when x0 meets the rule; b = 0 with x0 = 0 gives x = 0)
+ *   CFX_CG_MAX_ITER      max_iter updates were made
+ *   CFX_CG_BREAKDOWN     a sum of the recurrence is not finite (x is the iterate before), or the Krylov space was
+ *                        exhausted (gamma = 0: the update is finished first) without meeting the rule
+ *   CFX_CG_BAD_DIAGONAL  see above: x = x0 */
+#define CFX_PC_ABS_JACOBI 2
+#define CFX_PC_ABS_ROWSUM 3
+typedef cfx_cg_options cfx_minres_options;
+int cfx_minres_options_default(cfx_minres_options* opt); /* rtol 1e-10, atol 0, max_iter 10000, check_every 16,
+                                                            CFX_PC_ABS_JACOBI, lanes 0; works without a GPU */
+int cfx_minres_solve(int64_t nrows, const int64_t* indptr, const int32_t* indices, const double* values,
+                     const int32_t* rows, int64_t n_rows, const double* b, double* x /* in: x0, out: x */,
+                     const cfx_minres_options* opt /* or NULL: the defaults */, cfx_cg_info* info /* host or device pointer */);
+
 /* ---- float32 instantiation of the boundary --------------------------------------------------------------
  * python/cutfemx/wrappers/fem.cpp:490-500 declares the runtime assembly for <T, U> in {float, double}^2 and
  * wrappers/cut.cpp:403-407 the cut API for float and double: T = scalar type of MatrixCSR / Vector / Function,

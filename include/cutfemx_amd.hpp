@@ -654,6 +654,37 @@ inline void cg_solve(const SparsityPattern& pattern, const double* values, const
                      device_info));
 }
 
+/// cfx_minres_options with the library's defaults (rtol 1e-10, |diag| Jacobi, check_every 16 ...)
+struct MinresOptions : cfx_minres_options
+{
+  MinresOptions() { check(cfx_minres_options_default(this)); }
+};
+
+/// Diagonally preconditioned MINRES in HBM (cfx_minres_solve) on a SYMMETRIC, possibly indefinite system -- the merged
+/// saddle-point matrix of a cut Stokes problem: replaces the spsolve of python/demo/demo_stokes.py:39-60.  Symmetry on the
+/// iterated rows is required and not checked.  Arguments and reasons as for cg_solve; the stopping rule is
+/// |r|_{M^-1} <= max(rtol |b|_{M^-1}, atol) and the info holds these two norms.
+inline cfx_cg_info minres_solve(const SparsityPattern& pattern, const double* values, std::span<const double> b,
+                                std::span<double> x, const cfx_minres_options& options = MinresOptions(),
+                                const std::int32_t* rows = nullptr, std::int64_t n_rows = 0)
+{
+  if ((std::int64_t)b.size() != pattern.view.nrows || x.size() != b.size() || pattern.view.ncols != pattern.view.nrows)
+    throw std::invalid_argument("minres_solve: a square matrix and one entry of b and x per row");
+  cfx_cg_info info{};
+  check(cfx_minres_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b.data(),
+                         x.data(), &options, &info));
+  return info;
+}
+/// ... with the cfx_cg_info left in HBM (`device_info`): with device `b` / `x` and options.check_every = 0 the call
+/// makes no host round trip
+inline void minres_solve(const SparsityPattern& pattern, const double* values, const double* b, double* x,
+                         const cfx_minres_options& options, cfx_cg_info* device_info, const std::int32_t* rows = nullptr,
+                         std::int64_t n_rows = 0)
+{
+  check(cfx_minres_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b, x, &options,
+                         device_info));
+}
+
 /// One block of a MatrixCSR block system: the values of A[i][j] with their pattern (nullptr: an absent block)
 struct MatrixBlock
 {
