@@ -117,7 +117,7 @@ SYMBOLS = [
     "cfx_rules_physical_points", "cfx_rules_destroy", "cfx_evaluate_normals",
     "cfx_evaluate_values", "cfx_ghost_penalty_facets", "cfx_interior_facets_for_cells", "cfx_cell_aggregation_create", "cfx_cell_aggregation_view_get",
     "cfx_cell_aggregation_destroy", "cfx_cut_destroy", "cfx_space_create",
-    "cfx_space_static_bytes", "cfx_space_lattice_rows", "cfx_space_lattice_source_rows", "cfx_space_source_shell_hexes", "cfx_space_destroy", "cfx_form_create", "cfx_form_create2", "cfx_form_destroy", "cfx_form_prepare", "cfx_form_lattice_tile_lists", "cfx_create_sparsity",
+    "cfx_space_static_bytes", "cfx_space_lattice_rows", "cfx_space_lattice_source_rows", "cfx_space_lattice_pattern_rows", "cfx_space_source_shell_hexes", "cfx_space_destroy", "cfx_form_create", "cfx_form_create2", "cfx_form_destroy", "cfx_form_prepare", "cfx_form_lattice_tile_lists", "cfx_create_sparsity",
     "cfx_pattern_view_get", "cfx_pattern_reuse_stats", "cfx_pattern_destroy", "cfx_assemble_matrix", "cfx_assemble_matrix_zeroed", "cfx_assemble_vector", "cfx_assemble_scalar",
     "cfx_apply_lifting", "cfx_set_bc", "cfx_zero_rows", "cfx_csr_block_merge", "cfx_csr_permute", "cfx_tabulate_entity", "cfx_active_domain", "cfx_active_view", "cfx_deactivate_outside",
     "cfx_active_destroy", "cfx_csr_spmv", "cfx_cg_options_default", "cfx_cg_solve", "cfx_minres_options_default", "cfx_minres_solve",

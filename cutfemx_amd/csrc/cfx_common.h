@@ -661,6 +661,15 @@ struct Stencil
   // taken", cfx_space_lattice_rows): nothing in the assembly reads it.  It costs the streaming role one global atomic
   // per block and launch (at most 4096).
   DevArray<unsigned long long> lat_written;
+  // Index lattice (cfx::space_lattice, the same build): the numbering of every flagged row is a translate of
+  // lat_rstar's as well -- nbr[offsets[r] + k] - r == lat_idx[k] for k < lat_len.  One answer for the space: a single
+  // flagged row off it leaves lat_idx_ok false (a scrambled numbering keeps its geometry flags).  The column list of a
+  // complete flagged row is then r + lat_idx[k], which the streaming role of pattern_plain_tiles_kernel writes without
+  // reading the stencil.  lat_pat_written: rows whose columns it wrote so far (diagnostics only, like lat_written).
+  static constexpr int kLatIdxMax = 48; // (the offsets travel in the build's one 256 B read-back, behind its 8 numbers)
+  bool lat_idx_ok = false;
+  int32_t lat_idx[kLatIdxMax] = {};
+  DevArray<unsigned long long> lat_pat_written;
   // Closed-form series source term on the lattice rows (cfx::lattice_source_moments, 3-D): the vertex star of
   // lat_rstar as read back once -- per incident cell the four fl(x_v - x_r*) and the local index of r* -- and, per
   // quadrature degree, the eight moments T[sigma] of that star (bit d of sigma: sin(pi delta_d) instead of cos).
@@ -721,6 +730,18 @@ __device__ __forceinline__ bool lattice_template_row(unsigned diagpos_raw, unsig
 {
   return (diagpos_raw & kLatFlag) != 0 && __popc(umark & inline_bits) == 1 && mask == full;
 }
+// A plain row whose column list is written from the offset row of an index lattice (Stencil::lat_idx, where the space's
+// lat_idx_ok holds): flagged, its whole stencil present.  The cell marks do not enter -- the columns of a plain row
+// depend on its mask alone -- so lattice_template_row implies this rule.  The ONE statement of it: the streaming role
+// of pattern_plain_tiles_kernel that writes such rows and its tile role that leaves them out must agree row for row.
+__device__ __forceinline__ bool lattice_pattern_row(unsigned diagpos_raw, unsigned long long mask, unsigned long long full)
+{
+  return (diagpos_raw & kLatFlag) != 0 && mask == full;
+}
+// Plain rows of the plan from which build_pattern takes that path (CFX_LATTICE_PATTERN=2: always), like
+// kSourceShellMinEntities of the source term's shell path.  Measured: even at 128^3
+// (0.26 M plain rows) and 256^3 (2.1 M), 0.33 ms of the step at 512^3 (17.1 M); the bound lies between the last two.
+constexpr int64_t kLatticePatternMinRows = 6000000;
 // A row of a linear form whose series source term is the closed form in its own coordinates (cfx::lattice_source_moments):
 // it has a slot in the hex-corner staging (vec_t2off != 0: plain, every cell around it carries the mark) and is flagged.
 // The ONE statement of this rule as well: the fold that evaluates the closed form for such rows, the hex kernel that
@@ -1057,6 +1078,9 @@ const Stencil& space_lattice(cfx_space_s* V);                           // cfx_r
 bool lattice_template(cfx_space_s* V);                                  // cfx_gather.hip (Stencil::lat_tmpl)
 const double* lattice_source_moments(cfx_space_s* V, int qdegree);      // cfx_rowasm.hip (Stencil::lat_src_T; null: none)
 bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits);
+// mark bits of the cell slots whose uncut entities the P1 kernels compute as inline stiffness rows (RowIntegral::
+// std_inline == 2): what build_pattern and run_matrix both hand to plain_lattice_tiles
+unsigned p1_inline_bits(const cfx_form_s* a, const cfx_row_plan& plan); // cfx_rowasm.hip
 void lattice_tile_lists(cfx_form_s* a, int64_t* n_plain, int64_t* n_tiles, int32_t* plain_rows, uint8_t* templ,
                         int32_t* tile_first, int32_t* tile_id);         // cfx_rowasm.hip (cfx_form_lattice_tile_lists)          // cfx_rowasm.hip (cfx_row_plan::lat_tile_first)
 bool space_dof_verts(cfx_space_s* V);                                   // cfx_rowasm.hip (cfx_space_s::dof_verts)

@@ -1910,6 +1910,17 @@ int cfx_space_lattice_source_rows(cfx_space_t V, int64_t* rows)
   CFX_API_END
 }
 
+int cfx_space_lattice_pattern_rows(cfx_space_t V, int64_t* rows)
+{
+  CFX_API_BEGIN
+  require(V && rows, CFX_ERR_INVALID_ARGUMENT, "cfx_space_lattice_pattern_rows: null argument");
+  *rows = 0;
+  // (a query builds nothing: without the lattice table of the space no pattern can have taken the path)
+  const cfx::Stencil& S = V->stencil;
+  if (S.lat_built && S.lat_rows > 0 && S.lat_pat_written.p) *rows = (int64_t)cfx::read_scalar(S.lat_pat_written.p);
+  CFX_API_END
+}
+
 int cfx_space_source_shell_hexes(cfx_space_t V, int64_t* hexes)
 {
   CFX_API_BEGIN

@@ -4517,13 +4517,11 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
     bool split = false;
     if constexpr (DEG == 1)
     {
-      unsigned inline_bits = 0;
+      // (the slots with std_inline == 2 -- stated once, for build_pattern to hand plain_lattice_tiles the same bits)
+      const unsigned inline_bits = p1_inline_bits(a, plan);
       bool all_inline = A.iso_geometry != 0 && mr <= 64;
       for (int s = 0; s < A.n_cell; ++s)
-      {
-        if (A.cell[s].std_inline == 2) inline_bits |= 1u << s;
-        else if (A.cell[s].std_bits) all_inline = false; // staged uncut tensors: generic path
-      }
+        if (A.cell[s].std_inline != 2 && A.cell[s].std_bits) all_inline = false; // staged uncut tensors: generic path
       const bool split_p1 = all_inline && inline_bits && (2 * plan.n_special_rows.hint() <= plan.n_active_rows.hint() || env_is<Sw::ROWS_SPLIT>('1'));
       // (only when P was laid out from this very plan: a pattern of a larger form -- several forms assembled into one
       // matrix -- has full-length rows where this plan has none, and they must all be zeroed)

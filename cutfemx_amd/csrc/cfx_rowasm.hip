@@ -1813,37 +1813,104 @@ __global__ void tile_ids_kernel(DevN n_d, const int32_t* __restrict__ first, con
 // pass 2 by row tile (Stencil tiles, plan.plain_tile_first / _id): the rows of a tile are neighbours in the stencil
 // and in the CSR arrays.  A tile whose kRowTile rows are all plain and hold their whole stencil -- the bulk of the
 // domain -- is one contiguous copy nbr[st_off[r0] ...] -> indices[indptr[r0] ...]; other tiles go row by row.
-__global__ void __launch_bounds__(kWave) pattern_plain_tiles_kernel(DevN n_tiles_d, const int32_t* __restrict__ tile_first,
-                                                                    const int32_t* __restrict__ tile_id, DevN n_plain_d,
-                                                                    const int32_t* __restrict__ rows,
-                                                                    const unsigned long long* __restrict__ masks,
-                                                                    const int64_t* __restrict__ off,
-                                                                    const int32_t* __restrict__ nbr,
-                                                                    const int64_t* __restrict__ indptr,
-                                                                    int32_t* __restrict__ indices, int64_t ndofs)
+// On an index lattice (Stencil::lat_idx_ok; lat_len = 0: none) the first `stream_blocks` blocks write the rows of
+// lattice_pattern_row as r + lat_idx[k], no stencil read and no per-tile chain of loads; the tile role then runs the
+// tiles of plan.lat_tile_first, in which such rows are not live.
+struct PatTileArgs
 {
-  const int64_t n_plain = dev_n(n_plain_d);
-  const int64_t n_tiles = dev_n(n_tiles_d);
+  DevN n_tiles;
+  const int32_t* tile_first;
+  const int32_t* tile_id;
+  DevN n_plain;
+  const int32_t* rows;
+  const unsigned long long* masks;
+  const int64_t* off;
+  const int32_t* nbr;
+  const uint8_t* diagpos;
+  const int64_t* indptr;
+  int32_t* indices;
+  DevN nnz;      // every store is bounded by it: in a void step indptr may hold anything
+  int64_t ndofs;
+  int lat_len;
+  unsigned stream_blocks; // a multiple of 8
+  unsigned lat_recip;     // ceil(2^32 / lat_len): entry e of a pass is row e / lat_len = umulhi(e, lat_recip), e < 4096
+  unsigned long long* written;
+  int32_t lat_idx[Stencil::kLatIdxMax];
+};
+
+__global__ void __launch_bounds__(kWave) pattern_plain_tiles_kernel(PatTileArgs A)
+{
+  const int64_t n_plain = dev_n(A.n_plain);
+  const int64_t nnz = dev_n(A.nnz);
   constexpr int G = kWave / kRowTile;
   const int lane = threadIdx.x, g = lane / G, gl = lane % G;
-  const int64_t w = blockIdx.x;
+  const int L = A.lat_len;
+  const unsigned long long fullmask = L > 0 ? (1ull << L) - 1ull : 0ull;
+  if (blockIdx.x < A.stream_blocks)
+  {
+    // ---- streaming role: 64 plain rows per pass; the rows of the rule are ranked, their CSR offsets and numbers staged
+    // in LDS, and the lanes run over the lat_len * (rows) entries -- consecutive rows are one contiguous span
+    __shared__ int64_t s_ip[kWave];
+    __shared__ int32_t s_row[kWave];
+    __shared__ int32_t s_d[kWave];
+    if (lane < L) s_d[lane] = A.lat_idx[lane];
+    unsigned long long written = 0;
+    for (int64_t c = blockIdx.x; c * kWave < n_plain; c += A.stream_blocks)
+    {
+      const int64_t i = c * kWave + lane;
+      bool take = false;
+      int32_t rw = 0;
+      int64_t ip = 0;
+      if (i < n_plain)
+      {
+        rw = A.rows[i];
+        take = lattice_pattern_row(A.diagpos[rw], A.masks[i], fullmask);
+        if (take) ip = A.indptr[rw];
+      }
+      const unsigned long long tk = __ballot(take);
+      const int ntake = __popcll(tk);
+      if (take)
+      {
+        const int j = __popcll(tk & ((1ull << lane) - 1ull));
+        s_ip[j] = ip; s_row[j] = rw;
+      }
+      __syncthreads();
+      const unsigned total = (unsigned)(ntake * L);
+      for (unsigned e = lane; e < total; e += kWave)
+      {
+        const unsigned j = __umulhi(e, A.lat_recip), k = e - j * (unsigned)L;
+        const int64_t p = s_ip[j] + k;
+        if (p >= 0 && p < nnz) A.indices[p] = s_row[j] + s_d[k];
+      }
+      written += (unsigned long long)ntake;
+      __syncthreads();
+    }
+    if (lane == 0 && written) atomicAdd(A.written, written);
+    return;
+  }
+  const int64_t n_tiles = dev_n(A.n_tiles);
+  const int64_t w = (int64_t)blockIdx.x - A.stream_blocks;
   if (w >= n_tiles) return;
-  const int64_t i0 = tile_first[w], t = tile_id[w], r0 = t * kRowTile;
+  const int64_t i0 = A.tile_first[w], t = A.tile_id[w], r0 = t * kRowTile;
   int32_t rl = -1;
-  if (lane < kRowTile && i0 + lane < n_plain) rl = rows[i0 + lane];
+  if (lane < kRowTile && i0 + lane < n_plain) rl = A.rows[i0 + lane];
   unsigned pm = (rl >= 0 && rl / kRowTile == t) ? 1u << (rl % kRowTile) : 0u;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) pm |= __shfl_xor(pm, o, 64);
   const int64_t rr = r0 + (lane < kRowTile ? lane : kRowTile);
-  const int64_t so = off[rr < ndofs ? rr : ndofs], io = indptr[rr < ndofs ? rr : ndofs];
-  const bool live = (pm >> g) & 1u;
-  const unsigned long long m = live ? masks[i0 + __popc(pm & ((1u << g) - 1u))] : 0ull;
+  const int64_t so = A.off[rr < A.ndofs ? rr : A.ndofs], io = A.indptr[rr < A.ndofs ? rr : A.ndofs];
+  const unsigned dp = L > 0 ? A.diagpos[rr < A.ndofs ? rr : A.ndofs - 1] : 0u;
+  const bool plain = (pm >> g) & 1u;
+  const unsigned long long m = plain ? A.masks[i0 + __popc(pm & ((1u << g) - 1u))] : 0ull;
+  // (a row of the rule: the streaming role wrote it)
+  const bool pat = plain && L > 0 && lattice_pattern_row((unsigned)__shfl((int)dp, g, 64), m, fullmask);
+  const bool live = plain && !pat;
   const int64_t sb = __shfl(so, g, 64), ob = __shfl(io, g, 64);
   const int slen = (int)(__shfl(so, g + 1, 64) - sb);
   const bool full = live && (m & (m + 1ull)) == 0ull && __popcll(m) == slen;
   const int64_t sb0 = __shfl(so, 0, 64), ob0 = __shfl(io, 0, 64);
   const int nst = (int)(__shfl(so, kRowTile, 64) - sb0);
-  if (pm == 0xffffu && __ballot(!full) == 0ull && __shfl(io, kRowTile, 64) - ob0 == nst)
+  if (pm == 0xffffu && __ballot(!full) == 0ull && __shfl(io, kRowTile, 64) - ob0 == nst && ob0 >= 0 && ob0 + nst <= nnz)
   {
     // (eight loads in flight per lane -- a tile of a P1 space on a Kuhn mesh holds ~430 entries: all of them -- where one
     // load -> store per trip left the wavefront seven dependent latencies long)
@@ -1851,16 +1918,20 @@ __global__ void __launch_bounds__(kWave) pattern_plain_tiles_kernel(DevN n_tiles
     {
       int32_t v[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = j0 + lane + u * kWave < nst ? nbr[sb0 + j0 + lane + u * kWave] : 0;
+      for (int u = 0; u < 8; ++u) v[u] = j0 + lane + u * kWave < nst ? A.nbr[sb0 + j0 + lane + u * kWave] : 0;
 #pragma unroll
       for (int u = 0; u < 8; ++u)
-        if (j0 + lane + u * kWave < nst) indices[ob0 + j0 + lane + u * kWave] = v[u];
+        if (j0 + lane + u * kWave < nst) A.indices[ob0 + j0 + lane + u * kWave] = v[u];
     }
     return;
   }
   if (!live) return;
   for (int p = gl; p < slen; p += G)
-    if ((m >> p) & 1ull) indices[ob + __popcll(m & ((1ull << p) - 1ull))] = nbr[sb + p];
+    if ((m >> p) & 1ull)
+    {
+      const int64_t q = ob + __popcll(m & ((1ull << p) - 1ull));
+      if (q >= 0 && q < nnz) A.indices[q] = A.nbr[sb + p];
+    }
 }
 
 // Spaces with neighbour lists only (degree 2, vector-valued, DG): a plain row whose incident cells are ALL uncut
@@ -2827,6 +2898,30 @@ __global__ void __launch_bounds__(kBlock) lattice_flag_kernel(int64_t ndofs, con
   }
 }
 
+// Index lattice (Stencil::lat_idx_ok): is the numbering of every flagged row a translate of the representative's --
+// nbr[st_off[r] + k] - r the same numbers for all of them?  info[7] counts nothing, it is set on a mismatch; the
+// representative's own lane packs its offsets behind the 8 numbers, two int32 per word (flagged rows have its length).
+__global__ void __launch_bounds__(kBlock) lattice_index_kernel(int64_t ndofs, const int64_t* __restrict__ st_off,
+                                                               const int32_t* __restrict__ nbr,
+                                                               const uint8_t* __restrict__ diagpos,
+                                                               unsigned long long* __restrict__ info)
+{
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= ndofs) return;
+  const int64_t rs = (int64_t)info[1];
+  const int64_t sb = st_off[r], ss = st_off[rs];
+  const int len = (int)(st_off[rs + 1] - ss);
+  if (r == rs && len <= Stencil::kLatIdxMax)
+  {
+    int32_t* d = reinterpret_cast<int32_t*>(info + 8);
+    for (int k = 0; k < len; ++k) d[k] = (int32_t)((int64_t)nbr[ss + k] - rs);
+  }
+  if (!(diagpos[r] & kLatFlag)) return;
+  bool ok = true;
+  for (int k = 0; ok && k < len; ++k) ok = (int64_t)nbr[sb + k] - r == (int64_t)nbr[ss + k] - rs;
+  if (!ok) info[7] = 1ull;
+}
+
 __global__ void __launch_bounds__(kBlock) lattice_clear_kernel(int64_t ndofs, uint8_t* __restrict__ diagpos)
 {
   const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -2844,21 +2939,23 @@ const Stencil& space_lattice(cfx_space_s* V)
   if (S.lat_built || !S.tiles_usable) return S;
   if (!lattice_rows_on() || V->ndofs < 1 || V->mesh->x.n < 3 * V->ndofs) { S.lat_built = true; return S; }
   const Adjacency& adj = V->dof_cells();
-  DevArray<unsigned long long> info(8);
+  DevArray<unsigned long long> info(32); // 8 numbers | Stencil::kLatIdxMax int32 offsets of the index lattice
   info.zero();
   const dim3 grid = grid_for(V->ndofs, kBlock);
   launch("lattice_rows", lattice_maxc_kernel, grid, dim3(kBlock), 0, V->ndofs, adj.offsets.p, info.p);
   launch("lattice_rows", lattice_pick_kernel, dim3(1), dim3(kBlock), 0, V->ndofs, adj.offsets.p, S.offsets.p, info.p);
   launch("lattice_rows", lattice_flag_kernel, grid, dim3(kBlock), 0, V->ndofs, adj.offsets.p, S.slot4.p, S.offsets.p,
          S.nbr.p, V->mesh->x.p, S.diagpos.p, info.p);
+  launch("lattice_rows", lattice_index_kernel, grid, dim3(kBlock), 0, V->ndofs, S.offsets.p, S.nbr.p, S.diagpos.p, info.p);
   // One read-back of mesh-static numbers: it does not depend on the counts of a speculative step, so it is not put
   // under the step's void guard, and lat_built is set after it -- a throw leaves the flags to be written again.
-  unsigned long long h[8];
+  unsigned long long h[32];
+  static_assert(sizeof(h) == 256 && sizeof(h) == 64 + sizeof(int32_t) * Stencil::kLatIdxMax, "what pinned_scratch() holds");
   {
     unsigned long long* pin = static_cast<unsigned long long*>(pinned_scratch());
     CFX_HIP(hipMemcpyAsync(pin, info.p, sizeof(h), hipMemcpyDeviceToHost, ctx().stream));
     CFX_HIP(hipStreamSynchronize(ctx().stream));
-    for (int k = 0; k < 8; ++k) h[k] = pin[k];
+    for (int k = 0; k < 32; ++k) h[k] = pin[k];
     ++sync_counter();
   }
   const int64_t flagged = (int64_t)h[2], top = (int64_t)h[3];
@@ -2867,11 +2964,17 @@ const Stencil& space_lattice(cfx_space_s* V)
   {
     launch("lattice_rows", lattice_clear_kernel, grid, dim3(kBlock), 0, V->ndofs, S.diagpos.p);
     S.lat_rows = 0;
+    S.lat_idx_ok = false;
   }
   else
   {
     S.lat_written.alloc(1);
     S.lat_written.zero();
+    S.lat_pat_written.alloc(1);
+    S.lat_pat_written.zero();
+    // (a stencil of one entry has no offset row worth a path: lattice_pattern's reciprocal of lat_len needs >= 2)
+    S.lat_idx_ok = h[7] == 0 && h[6] >= 2 && (int)h[6] <= Stencil::kLatIdxMax;
+    memcpy(S.lat_idx, h + 8, sizeof(S.lat_idx));
     S.lat_src_written.alloc(1);
     S.lat_src_written.zero();
     S.lat_shell_ran.alloc(1);
@@ -3174,6 +3277,19 @@ void lattice_tile_lists(cfx_form_s* a, int64_t* n_plain, int64_t* n_tiles, int32
     const std::vector<int32_t> f = download(plan.lat_tile_id.p, nt);
     std::copy(f.begin(), f.end(), tile_id);
   }
+}
+
+unsigned p1_inline_bits(const cfx_form_s* a, const cfx_row_plan& plan)
+{
+  const cfx_space_s* V = a->V;
+  if (a->rank != 2 || V->degree != 1 || V->bs != 1 || V->dofmap.p != V->mesh->conn.p) return 0u;
+  unsigned bits = 0;
+  for (int s = 0; s < plan.n_cell_slots; ++s)
+  {
+    const cfx_integral_dev& I = a->integrals[plan.cell_slot_integral[s]];
+    if (I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0) bits |= 1u << s;
+  }
+  return bits;
 }
 
 bool plain_lattice_tiles(cfx_form_s* a, unsigned inline_bits)
@@ -4179,6 +4295,9 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
       P->nnz = Count(read_scalar(offs.p + ntiles));
     }
     P->indices.alloc(P->nnz.cap());
+    // CFX_STAGING_NAN=1 (tests): the block cache hands a step the previous step's buffer, in which a row that nobody
+    // wrote could still hold the right columns -- every index starts as -1, before the first writer
+    if (env_is<Sw::STAGING_NAN>('1') && P->nnz.cap() > 0) dev_fill(P->indices.p, 0xff, sizeof(int32_t) * (size_t)P->nnz.cap());
     if (chain.state)
       launch("pattern_indptr", indptr_chained_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs,
              plan.rowmark.p, counts.p, P->indptr.p, P->indices.p, P->nnz.cap(), chain, offs.p + ntiles, after);
@@ -4187,9 +4306,36 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
              plan.rowmark.p, counts.p, offs.p, P->indptr.p, P->indices.p, P->nnz.devn());
   }
   if (use_stencil && space_stencil_tiles(V).tiles_usable && plan.n_plain_tiles.cap() > 0)
-    launch("pattern_plain_write", pattern_plain_tiles_kernel, wave_grid(plan.n_plain_tiles.cap()), dim3(kWave), 0, plan.n_plain_tiles,
-           plan.plain_tile_first.p, plan.plain_tile_id.p, plan.n_plain_rows, plan.plain_rows.p, plan.plain_masks.p,
-           st.offsets.p, st.nbr.p, P->indptr.p, P->indices.p, V->ndofs);
+  {
+    PatTileArgs T{};
+    T.n_tiles = plan.n_plain_tiles; T.tile_first = plan.plain_tile_first.p; T.tile_id = plan.plain_tile_id.p;
+    T.n_plain = plan.n_plain_rows; T.rows = plan.plain_rows.p; T.masks = plan.plain_masks.p;
+    T.off = st.offsets.p; T.nbr = st.nbr.p; T.diagpos = st.diagpos.p; T.indptr = P->indptr.p; T.indices = P->indices.p;
+    T.nnz = P->nnz.devn(); T.ndofs = V->ndofs;
+    int64_t tile_blocks = plan.n_plain_tiles.cap();
+    // index lattice: the complete flagged rows are written from the offset row by the first blocks of the launch; the
+    // tile role then runs the tiles that hold a plain row off the MATRIX rule (plan.lat_tile_first, built here for
+    // the assembly to find) -- a superset of the tiles with a row off the pattern rule, which it checks row by row
+    const char sw = env_char<Sw::LATTICE_PATTERN>();
+    const unsigned bits = sw != '0' && V->bs == 1 ? p1_inline_bits(a, plan) : 0u;
+    if (bits && (sw == '2' || plan.n_plain_rows.hint() >= kLatticePatternMinRows))
+    {
+      const Stencil& lat = space_lattice(V);
+      if (lat.lat_rows > 0 && lat.lat_idx_ok && plain_lattice_tiles(a, bits))
+      {
+        T.lat_len = lat.lat_len; T.lat_recip = 0xffffffffu / (unsigned)lat.lat_len + 1u;
+        memcpy(T.lat_idx, lat.lat_idx, sizeof(T.lat_idx));
+        T.written = lat.lat_pat_written.p;
+        T.n_tiles = plan.n_lat_tiles; T.tile_first = plan.lat_tile_first.p; T.tile_id = plan.lat_tile_id.p;
+        tile_blocks = plan.n_lat_tiles.cap();
+        // >= 256 rows per wavefront, at most 16 wavefronts per CU in flight (as the values' streaming role)
+        const int64_t chunks = (plan.n_plain_rows.cap() + kWave - 1) / kWave;
+        T.stream_blocks = (unsigned)((std::min<int64_t>(std::max<int64_t>(chunks / 4, 1), 4096) + 7) / 8 * 8);
+      }
+    }
+    const int64_t blocks = (int64_t)T.stream_blocks + tile_blocks;
+    if (blocks > 0) launch("pattern_plain_write", pattern_plain_tiles_kernel, wave_grid(blocks), dim3(kWave), 0, T);
+  }
   else if (use_stencil)
     launch("pattern_plain_write", pattern_plain_write_kernel, grid_for(plan.n_plain_rows.cap() * CFX_PPW_LANES), dim3(kBlock), 0,
            plan.n_plain_rows, plan.plain_rows.p, plan.plain_masks.p, st.offsets.p, st.nbr.p, P->indptr.p, P->indices.p);

@@ -25,6 +25,7 @@
   CFX_SWITCH(TILES,              first_char, build, "0: no row tiles") \
   CFX_SWITCH(LATTICE_ROWS,       first_char, build, "0: no lattice flags and no template: every plain row is computed by the tile kernel") \
   CFX_SWITCH(LATTICE_SOURCE,     first_char, call,  "0: the P1 series source term of the lattice rows hex by hex instead of its closed form per row") \
+  CFX_SWITCH(LATTICE_PATTERN,    first_char, call,  "0: plain rows' columns always copied from the stencil; 2: from the offset row whatever the number of plain rows") \
   CFX_SWITCH(P2_PLAIN,           first_char, build, "0: degree 2 without the slot-record kernel") \
   CFX_SWITCH(P2_CLOSED,          first_char, call,  "0: degree 2 stages uncut tensors instead of closed-form rows") \
   CFX_SWITCH(P2_MOMENTS,         first_char, call,  "0: degree 2 stages cut-cell stiffness tensors instead of moments") \
@@ -39,7 +40,7 @@
   CFX_SWITCH(SOURCE_SERIES,      first_char, call,  "0: the P1 source term by quadrature instead of its series") \
   CFX_SWITCH(SOURCE_GROUPS,      first_char, call,  "0: the P1 series source term cell by cell instead of one hex per lane") \
   CFX_SWITCH(SOURCE_SHELL,       first_char, call,  "0: the hex kernel of the closed-form source term sifts every hex of the entity list instead of taking the shell hexes from the rows that read them; 2: shell hexes whatever the length of the list (default: from 4 M entities)") \
-  CFX_SWITCH(STAGING_NAN,        first_char, call,  "1 (tests): the hex-corner planes of the staging start as NaN") \
+  CFX_SWITCH(STAGING_NAN,        first_char, call,  "1 (tests): the hex-corner planes of the staging start as NaN, the column indices of a new pattern as -1") \
   CFX_SWITCH(PLAIN_STAGE,        first_char, call,  "0: plain rows without LDS staging, the form that meshes with stencils longer than 32 take by themselves") \
   CFX_SWITCH(MFMA,               first_char, call,  "0: generic rows instead of the MFMA kernel for staged elasticity tensors") \
   CFX_SWITCH(CUT_TENSORS_P1,     first_char, call,  "0: the generic tensors of cut P1 cells") \

@@ -225,6 +225,13 @@ class FunctionSpace:
         _lib.check(_lib.lib().cfx_space_lattice_source_rows(self._h, C.byref(n)))
         return int(n.value)
 
+    def lattice_pattern_rows(self) -> int:
+        """Plain rows whose column indices a sparsity build wrote from the offset row of the index lattice since the
+        space was created (cfx_space_lattice_pattern_rows); the difference across a build is that build's count."""
+        n = C.c_int64(0)
+        _lib.check(_lib.lib().cfx_space_lattice_pattern_rows(self._h, C.byref(n)))
+        return int(n.value)
+
     def source_shell_hexes(self) -> int:
         """Hexes the hex kernel of the series source term ran in the last assembly of a linear form on this space when
         it took the shell hexes from the rows that read them (cfx_space_source_shell_hexes); 0 otherwise."""

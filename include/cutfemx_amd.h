@@ -418,6 +418,13 @@ int cfx_space_lattice_rows(cfx_space_t V, int64_t* n, int64_t* template_rows);
  * mesh-static moments of the representative row's cells times sin / cos of the row's own coordinates; the result
  * differs from the cell loop's by rounding only.  0 without lattice rows, in 2-D, under CFX_LATTICE_SOURCE=0. */
 int cfx_space_lattice_source_rows(cfx_space_t V, int64_t* rows);
+/* Plain rows whose column indices cfx_create_sparsity wrote as r + d_k since the space was created (diagnostics; the
+ * difference across one cfx_create_sparsity call is that call's count).  Where the numbering of every lattice row (see
+ * above) is a translate of the representative row's as well -- neighbour k of row r is r + d_k, one offset row d for
+ * the space, as on the generated boxes -- a plain row that is a lattice row and holds its whole stencil takes its
+ * columns from d instead of a copy of its neighbour list; the arrays are the same.  0 without lattice rows, on a
+ * numbering that is no translate, for a form without an inline stiffness integral, under CFX_LATTICE_PATTERN=0. */
+int cfx_space_lattice_pattern_rows(cfx_space_t V, int64_t* rows);
 /* Hexes (cells 6h .. 6h+5 of a mesh of hex groups) the hex kernel of the series source term ran in the last assembly of
  * a linear form on this space, when it took them from the rows that read them: the hexes with a tet that is an entity
  * of the integral and has a corner row that does not take the closed form above.  0 when the last assembly did not go
