@@ -1330,44 +1330,33 @@ __global__ void deactivate_kernel(DevN n_d, const int32_t* __restrict__ rows, co
   if (b) b[r] = rhs_value;
 }
 
-// Deactivation straight from the row marks.  A tile of kByteTile rows that are ALL inactive (most inactive rows: the
-// region outside the domain) holds one entry per row, its diagonal (assembler.h:538-560: the all-rows diagonal of every
-// pattern this library builds; checked here: one entry per row through the tile's two row pointers, each entry its
-// row's diagonal through one coalesced read): row r0 + k sits k entries behind the tile's first row pointer, so the tile
-// is two contiguous fills.  The other tiles set their unmarked rows one by one.  tile_counts: active rows per tile
-// (special | plain << 32, cfx_row_plan::row_tile_counts).
+// Deactivation straight from the row marks.  A run of whole 16-row groups that are ALL inactive (wave_inactive_rows,
+// cfx_device.h; most inactive rows: the region outside the domain) holds one entry per row, its diagonal
+// (assembler.h:538-560: the all-rows diagonal of every pattern this library builds; checked here: one entry per row
+// through the run's two row pointers, each entry its row's diagonal through one coalesced read): row r + k sits k
+// entries behind the run's first row pointer, so the run is two contiguous fills.  A run that fails the check, and the
+// inactive rows of groups with active rows, are set one by one.  tile_counts: active rows per tile (special |
+// plain << 32, cfx_row_plan::row_tile_counts); 0: the tile's marks are not read.  A fill into `values` lies in [0, nnz).
+// own_pattern: the pattern was built from the plan of these very marks (cfx_pattern_s::built_plan, what the fused zero
+// fill relies on too): its unmarked rows were written as their diagonal by indptr_tile, and a run with one entry per
+// row is accepted without reading the entries back.
 __global__ void __launch_bounds__(kBlock) deactivate_marks_kernel(int64_t nrows, const uint8_t* __restrict__ rowmark,
                                                                   const int64_t* __restrict__ tile_counts,
                                                                   const int64_t* __restrict__ indptr,
                                                                   const int32_t* __restrict__ indices, double* __restrict__ values,
                                                                   double* __restrict__ b, double diagonal, double rhs_value, int* error,
-                                                                  DevN n_active_d, DevN nnz_d)
+                                                                  DevN n_active_d, DevN nnz_d, bool own_pattern)
 {
   // (lengths still in HBM: nothing to do in a void step -- marks and row pointers are not those of this step then)
   if (n_active_d.dev && dev_n(n_active_d) == 0) return;
   if (nnz_d.dev && dev_n(nnz_d) == 0) return;
-  const int64_t r0 = (int64_t)blockIdx.x * kByteTile;
-  const int tl = (int)min((int64_t)kByteTile, nrows - r0);
-  const int64_t tc = tile_counts[blockIdx.x];
-  const int nact = (int)((tc & 0xffffffffll) + (tc >> 32));
-  if (nact == 0 && (!values || indptr[r0 + tl] - indptr[r0] == tl))
+  static_assert(kByteTile == (kBlock / 64) * kWaveGroupRows, "a wavefront's groups per quarter of the tile");
+  const int64_t nnz = values ? dev_n(nnz_d) : 0;
+  const int64_t w0 = (int64_t)blockIdx.x * kByteTile + (int64_t)kWaveGroupRows * (threadIdx.x >> 6);
+  if (w0 >= nrows) return;
+  const int lane = threadIdx.x & 63;
+  auto one_row = [&](int64_t r)
   {
-    int ok = 1;
-    const int64_t e0 = values ? indptr[r0] : 0;
-    if (values)
-      for (int k = threadIdx.x; k < tl; k += kBlock) ok &= indices[e0 + k] == (int32_t)(r0 + k) ? 1 : 0;
-    if (__syncthreads_and(ok))
-    {
-      if (values) block_fill_run(values + e0, tl, diagonal);
-      if (b) block_fill_run(b + r0, tl, rhs_value);
-      return;
-    }
-  }
-  if (nact == tl) return;
-  for (int k = threadIdx.x; k < tl; k += kBlock)
-  {
-    const int64_t r = r0 + k;
-    if (rowmark[r]) continue;
     if (values)
     {
       const int64_t rb = indptr[r], re = indptr[r + 1];
@@ -1375,7 +1364,25 @@ __global__ void __launch_bounds__(kBlock) deactivate_marks_kernel(int64_t nrows,
       if (pos < 0) *error = 1; else values[pos] = diagonal;
     }
     if (b) b[r] = rhs_value;
-  }
+  };
+  wave_inactive_rows(
+      rowmark, values ? indptr : (const int64_t*)nullptr, w0, nrows, tile_counts[blockIdx.x] == 0,
+      [&](int64_t r, int n, int64_t e0, int64_t e1)
+      {
+        if (values)
+        {
+          bool diag = e0 >= 0 && e0 + n <= nnz && e1 - e0 == n;
+          if (diag && !own_pattern) diag = __all(iota_run_holds(indices + e0, n, (int32_t)r, lane, 64)) != 0;
+          if (!diag)
+          {
+            for (int k = lane; k < n; k += 64) one_row(r + k);
+            return;
+          }
+          fill_run(values + e0, n, diagonal, lane, 64);
+        }
+        if (b) fill_run(b + r, n, rhs_value, lane, 64);
+      },
+      one_row);
 }
 
 __global__ void inactive_tile_counts_kernel(int64_t ntiles, int64_t n, const int64_t* __restrict__ active, int32_t* __restrict__ zeros)
@@ -2851,12 +2858,12 @@ int cfx_deactivate_outside(cfx_active_t d, cfx_pattern_t P, double* values, doub
   const int64_t ntiles = (nrows + kByteTile - 1) / kByteTile;
   if (d->V->bs == 1 && plan.row_tile_counts.n == ntiles && (!values || P->nrows == nrows))
   {
-    // straight from the row marks, tile by tile: a tile of kByteTile inactive rows is two contiguous fills, the other
-    // tiles set their inactive rows one by one -- no list of inactive dofs is built
+    // straight from the row marks: a run of 16-row groups of inactive rows is two contiguous fills, the inactive rows
+    // of the other groups are set one by one -- no list of inactive dofs is built
     launch("deactivate", deactivate_marks_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, nrows, plan.rowmark.p,
            plan.row_tile_counts.p, values ? P->indptr.p : (const int64_t*)nullptr, values ? P->indices.p : (const int32_t*)nullptr,
            values ? ov->dev : (double*)nullptr, b ? ob->dev : (double*)nullptr, diagonal, rhs_value, err.p,
-           plan.n_active_rows.devn(), values ? P->nnz.devn() : DevN());
+           plan.n_active_rows.devn(), values ? P->nnz.devn() : DevN(), values && P->built_plan == plan.serial);
   }
   else
   {

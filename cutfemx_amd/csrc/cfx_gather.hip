@@ -3244,29 +3244,33 @@ __global__ void __launch_bounds__(kBlock) zero_inactive_rows_kernel(int64_t nrow
   for (int64_t k = max(indptr[R], (int64_t)0); k < e1; ++k) values[k] = 0.0;
 }
 
-// ... scalar spaces with the plan's per-tile row counts: a tile of kByteTile rows without an active row is kByteTile
-// consecutive diagonal entries -- one contiguous fill from the tile's first row pointer, no per-row reads
+// ... scalar spaces: the entries of consecutive inactive rows are one contiguous range, whatever the rows hold -- a run
+// of whole 16-row groups without an active row (wave_inactive_rows, cfx_device.h) is one fill between its two row
+// pointers; only the inactive rows of groups with active rows go one by one.  tile_counts (the plan's active rows per
+// tile of kByteTile rows) == 0: the tile's marks are not read.  Every store is at a position in [0, nnz).
 __global__ void __launch_bounds__(kBlock) zero_inactive_tiles_kernel(int64_t nrows, const uint8_t* __restrict__ rowmark,
                                                                      const int64_t* __restrict__ tile_counts,
                                                                      const int64_t* __restrict__ indptr, double* __restrict__ values,
                                                                      DevN nnz_d)
 {
+  static_assert(kByteTile == (kBlock / 64) * kWaveGroupRows, "a wavefront's groups per quarter of the tile");
   const int64_t nnz = dev_n(nnz_d);
   if (nnz == 0) return;
-  const int64_t r0 = (int64_t)blockIdx.x * kByteTile;
-  const int n = (int)min((int64_t)kByteTile, nrows - r0);
-  if (tile_counts[blockIdx.x] == 0)
-  {
-    const int64_t e0 = indptr[r0];
-    if (e0 >= 0 && e0 + n <= nnz) block_fill_run(values + e0, n, 0.0);
-    return;
-  }
-  for (int k = threadIdx.x; k < n; k += kBlock)
-    if (!rowmark[r0 + k])
-    {
-      const int64_t e1 = min(indptr[r0 + k + 1], nnz);
-      for (int64_t e = max(indptr[r0 + k], (int64_t)0); e < e1; ++e) values[e] = 0.0;
-    }
+  const int64_t w0 = (int64_t)blockIdx.x * kByteTile + (int64_t)kWaveGroupRows * (threadIdx.x >> 6);
+  if (w0 >= nrows) return;
+  const int lane = threadIdx.x & 63;
+  wave_inactive_rows(
+      rowmark, indptr, w0, nrows, tile_counts[blockIdx.x] == 0,
+      [&](int64_t, int, int64_t p0, int64_t p1)
+      {
+        const int64_t e0 = max(p0, (int64_t)0), e1 = min(p1, nnz);
+        if (e0 < e1) fill_run(values + e0, e1 - e0, 0.0, lane, 64);
+      },
+      [&](int64_t r)
+      {
+        const int64_t e1 = min(indptr[r + 1], nnz);
+        for (int64_t e = max(indptr[r], (int64_t)0); e < e1; ++e) values[e] = 0.0;
+      });
 }
 
 // stage 2, linear forms: b[r] += sum over the marked incident cells of be[local row]

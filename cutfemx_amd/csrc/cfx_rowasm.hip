@@ -1152,44 +1152,95 @@ __device__ __forceinline__ int64_t indptr_tile(int64_t nrows, int bs, const uint
                                                const int64_t nnz_cap)
 {
   __shared__ int64_t s_v[kTile];
-  // A whole tile of inactive rows of a scalar space (87 % of the rows at 512^3): indptr is an arithmetic progression and
-  // the diagonal entries are the row numbers -- eight rows per thread as 16 B stores, no marks gathered row by row, no
-  // LDS scan.
+  // A whole tile of a scalar space, no division: a thread holds the marks of its eight consecutive rows (one 8 B load)
+  // and their row pointers in registers.  Consecutive inactive rows hold one entry each, their own number: the diagonal
+  // entries of a run are an iota run (cfx_device.h) from the run's first row pointer, and indptr leaves through LDS --
+  // consecutive lanes on consecutive 16 B words in both.  Every store into `indices` is at a position in [0, nnz_cap)
+  // (a negative one: a void step -- the lengths of marked rows before it were never written and summed to garbage).
   if (bs == 1 && tile + kTile <= nrows)
   {
-    static_assert(kScanItems == 8, "eight rows per thread");
-    const uint2 m = *reinterpret_cast<const uint2*>(rowmark + tile + 8 * threadIdx.x); // (tile and 8 t: 8 B aligned)
-    if (__syncthreads_or((m.x | m.y) != 0u) == 0)
+    static_assert(kScanItems == 8 && 2 * kScanItems == kGroupRows, "eight rows per thread, a 16-row group per lane pair");
+    const int64_t r0 = tile + 8 * threadIdx.x;
+    const uint2 m = *reinterpret_cast<const uint2*>(rowmark + r0); // (tile and 8 t: 8 B aligned)
+    const bool none = (m.x | m.y) == 0u;
+    auto diag_run = [&](int64_t p, int64_t r, int n, int t, int nt) // rows r .. r + n - 1 at p ..: the part inside [0, nnz_cap)
     {
+      const int64_t lo = max(p, (int64_t)0), hi = min(p + n, nnz_cap);
+      if (lo < hi) iota_run(indices + lo, (int)(hi - lo), (int32_t)(r + (lo - p)), t, nt);
+    };
+    const bool wide = (reinterpret_cast<uintptr_t>(indptr + tile) & 15) == 0;
+    auto indptr_out = [&](auto value) // value(i): row pointer of row tile + i
+    {
+      if (wide)
+      {
+        longlong2* ip = reinterpret_cast<longlong2*>(indptr + tile);
+#pragma unroll
+        for (int k = 0; k < kScanItems / 2; ++k)
+        {
+          const int i = k * kBlock + threadIdx.x;
+          ip[i] = make_longlong2(value(2 * i), value(2 * i + 1));
+        }
+      }
+      else
+      {
+#pragma unroll
+        for (int k = 0; k < kScanItems; ++k) indptr[tile + k * kBlock + threadIdx.x] = value(k * kBlock + threadIdx.x);
+      }
+    };
+    if (__syncthreads_or(!none) == 0)
+    {
+      // no active row (87 % of the rows at 512^3): indptr is an arithmetic progression, no lengths, no scan
       const int64_t t0 = first((int64_t)kTile);
-      const int64_t p0 = t0 + 8 * threadIdx.x;
-      const int64_t r0 = tile + 8 * threadIdx.x;
-      if ((reinterpret_cast<uintptr_t>(indptr + r0) & 15) == 0)
-      {
-        longlong2* ip = reinterpret_cast<longlong2*>(indptr + r0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ip[q] = make_longlong2(p0 + 2 * q, p0 + 2 * q + 1);
-      }
-      else
-      {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) indptr[r0 + q] = p0 + q;
-      }
-      // (the diagonal entries one by one: as 16 B words from the first aligned position on -- t0 is whatever the active
-      // rows before the tile add up to -- the kernel ran 0.63 instead of 0.51 ms at 512^3)
-      // (p0 < 0: a void step -- the lengths of marked rows before this tile were never written and summed to garbage)
-      if (p0 >= 0 && p0 + 8 <= nnz_cap)
-      {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) indices[p0 + q] = (int32_t)(r0 + q);
-      }
-      else
-      {
-        for (int q = 0; q < 8; ++q)
-          if (p0 + q >= 0 && p0 + q + 1 <= nnz_cap) indices[p0 + q] = (int32_t)(r0 + q);
-      }
+      indptr_out([&](int i) { return t0 + i; });
+      diag_run(t0, tile, kTile, threadIdx.x, kBlock);
       return t0 + kTile;
     }
+    // the lengths of a thread's marked rows: two 16 B loads (r0 a multiple of 8, counts holds every row)
+    int64_t v[kScanItems], s = 0;
+    {
+      int4 c0 = make_int4(1, 1, 1, 1), c1 = c0;
+      if (!none)
+      {
+        c0 = reinterpret_cast<const int4*>(counts + r0)[0];
+        c1 = reinterpret_cast<const int4*>(counts + r0)[1];
+      }
+      const int c[kScanItems] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+#pragma unroll
+      for (int q = 0; q < kScanItems; ++q)
+      {
+        v[q] = (((q < 4 ? m.x : m.y) >> (8 * (q & 3))) & 0xffu) ? (int64_t)c[q] : 1;
+        s += v[q];
+      }
+    }
+    int64_t total;
+    const int64_t local = block_exclusive_scan<int64_t>(s, total);
+    const int64_t t0 = first(total);
+    const int64_t p0 = local + t0;
+    {
+      int64_t off = p0;
+#pragma unroll
+      for (int q = 0; q < kScanItems; ++q) { s_v[threadIdx.x * kScanItems + q] = off; off += v[q]; }
+    }
+    __syncthreads();
+    indptr_out([&](int i) { return s_v[i]; });
+    // diagonal entries: a 16-row group is a lane pair; maximal runs of groups without an active row, wavefront by
+    // wavefront, then the inactive rows of the other groups one by one from the registers
+    const int lane = threadIdx.x & 63;
+    const bool uniform = none && __shfl_xor((int)none, 1, 64) != 0;
+    unsigned long long runs = __ballot(uniform);
+    int f, c;
+    while (take_bit_run(runs, f, c)) diag_run(__shfl(p0, f, 64), r0 + 8 * (f - lane), 8 * c, lane, 64);
+    if (!uniform)
+    {
+      int64_t p = p0;
+#pragma unroll
+      for (int q = 0; q < kScanItems; ++q)
+      {
+        if ((((q < 4 ? m.x : m.y) >> (8 * (q & 3))) & 0xffu) == 0u && p >= 0 && p < nnz_cap) indices[p] = (int32_t)(r0 + q);
+        p += v[q];
+      }
+    }
+    return t0 + total;
   }
 #pragma unroll
   for (int k = 0; k < kScanItems; ++k)
