@@ -1,4 +1,4 @@
-"""GPU rehearsal of the multi-GPU path on one card: two processes, both on
+"""GPU rehearsal of the multi-GPU path on one card: two or three processes, all on
 cuda:0, gloo transport (RCCL cannot put two ranks on one device), the real HIP
 engine per rank.  Owned rows must equal the serial oracle matrix / vector."""
 import os
@@ -53,20 +53,26 @@ def _worker(rank, world, port, n, q, mode):
         errb = np.abs(b[rows] - bref[rows + part.vertex_offset]).max() / np.abs(bref).max()
         gi = gref["inactive"]
         want_inactive = gi[(gi >= r_lo + part.vertex_offset) & (gi < r_hi + part.vertex_offset)] - part.vertex_offset
+        # after the second step every halo plane that step_owner poisoned has been filled by its owner
+        nan_free = not bool(torch.isnan(dp.phi_values).any())
         q.put((rank, float(err), float(errb), bool(np.array_equal(own_inactive, want_inactive)),
-               int(info["active_dofs_owned"])))
+               int(info["active_dofs_owned"]), nan_free))
     finally:
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("mode", ["owner", "reduce", "owner+device"])
-def test_two_ranks_on_one_gpu_match_serial(oracle, mode):
+@pytest.mark.parametrize("world,mode", [(2, "owner"), (2, "reduce"), (2, "owner+device"), (3, "owner"), (3, "reduce")])
+def test_ranks_on_one_gpu_match_serial(oracle, world, mode):
+    """world = 3 at n = 16 (slab bounds [0, 5, 7, 16] in owner mode, [0, 6, 8, 16] in reduce mode): rank 1 is a middle
+    rank, as six of the eight ranks of the target run are -- a slab with z0 > 0 and an upper halo, halo planes from
+    both neighbours in one scatter_forward (owner), two row exchanges in one scatter_reverse_matrix (reduce)."""
     import torch.multiprocessing as mp
     n = 16
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = 29600 + (os.getpid() % 2000) + {"owner": 7, "reduce": 0, "owner+device": 13}[mode]
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, n, q, mode)) for r in range(2)]
+    port = 29600 + (os.getpid() % 2000) + {(2, "owner"): 7, (2, "reduce"): 0, (2, "owner+device"): 13, (3, "owner"): 19,
+                                           (3, "reduce"): 23}[(world, mode)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, n, q, mode)) for r in range(world)]
     for p in procs:
         p.start()
     res = [q.get(timeout=600) for _ in procs]
@@ -77,10 +83,12 @@ def test_two_ranks_on_one_gpu_match_serial(oracle, mode):
     gm = oracle.mesh_box(3, n)
     gref = oracle_poisson(oracle, gm, level_set_values(gm.x, 3))
     total_active = 0
-    for rank, err, errb, inactive_ok, active in res:
+    assert sorted(r[0] for r in res) == list(range(world))
+    for rank, err, errb, inactive_ok, active, nan_free in res:
         assert err < 1e-12, (rank, err)
         assert errb < 1e-12, (rank, errb)
         assert inactive_ok
+        assert nan_free, f"rank {rank}: a poisoned halo plane of phi was not filled"
         total_active += active
     assert total_active == gm.nnodes - gref["inactive"].size
 
