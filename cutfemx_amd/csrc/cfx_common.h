@@ -590,7 +590,7 @@ struct OutArray
 };
 
 // ---------------------------------------------------------------------------
-// device primitives (cfx_primitives.hip)
+// device primitives (cfx_runtime.hip)
 // ---------------------------------------------------------------------------
 // out[0..n] = exclusive scan of in[0..n-1]; out[n] = total
 // `after` (optional): counts whose sources are complete once this scan has written its total (cfx::CountPlan)
