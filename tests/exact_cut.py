@@ -547,6 +547,8 @@ CASES = {
     "3d-n5-gyroid": (3, 5, "gyroid", False, None, (4,)),
     # the scrambled mesh on which the two cells of most ghost facets differ in diameter (H_CASE of the facet terms)
     "2d-n8-sphere-scrambled": (2, 8, "sphere", True, None, (2, 4)),
+    # 1248 P1 extension pairs at threshold 1.0, 333 bad cells on one root (the pair forms)
+    "3d-n6-gyroid": (3, 6, "gyroid", False, None, (2,)),
 }
 
 
@@ -1061,3 +1063,159 @@ def facet_case(O, name):
                     inside_keep=~both0[neg], ghost=ghost, ghost_keep=~(allzero[ghost[:, 0]] & allzero[ghost[:, 2]]),
                     n_cut_cut=int((kinds == 2).sum()), n_cut_inside=int((kinds == 1).sum()), h=h)
     return cached(("facets", name), run)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# extension penalty: the (bad, root) pair block, and the volume fractions that decide which cells are roots
+# ---------------------------------------------------------------------------------------------------------------------
+# beta int_{K_bad} M_i M_j with M = [N_bad, -(N_root o F_root^-1)]: the root's basis functions are polynomials of the
+# physical point and are taken on the bad cell, outside the root.  The root's barycentric coordinates are an affine,
+# rational function of the bad cell's, so at the rational Grundmann-Moeller points of the bad cell every factor is a
+# rational number and the rule of index s, 2 s + 1 >= 2 degree, gives the integral itself.
+def root_coordinates(Xb, Xr):
+    """(P, D): lambda_k of the simplex Xr at vertex v of the simplex Xb is P[v][k] / D (Cramer's rule on
+    sum_k lambda_k (1, x_k) = (1, p)); rows of Fractions."""
+    A = [[F(1)] + list(r) for r in Xr]
+    P = [[det(A[:k] + [[F(1)] + list(p)] + A[k + 1:]) for k in range(len(Xr))] for p in Xb]
+    return P, det(A)
+
+
+def _basis_numerators(n, Q, d, degree):
+    """Numerators of the nodal basis over Q^degree at the point with barycentric coordinates n / Q (integers)."""
+    if degree == 1:
+        return list(n)
+    return [v * (2 * v - Q) for v in n] + [4 * n[a] * n[b] for a, b in EDGES[d]]
+
+
+def pair_tensor_exact(x, conn, tdim, degree, bad, root, beta=1):
+    """The scalar (2 ND)^2 pair block as Fractions (rows of a list), layout [[bad bad, bad root], [root bad, root root]].
+    Integer arithmetic inside: float64 inputs are dyadic, so one power of two clears P and D of `root_coordinates`; at
+    a Grundmann-Moeller point (odd integers) / den the bad cell's coordinates are integers over den and the root's are
+    integers over den * D."""
+    d = tdim
+    Xb, Xr = frac_rows(x[conn[bad], :d]), frac_rows(x[conn[root], :d])
+    P, D = root_coordinates(Xb, Xr)
+    if D == 0:
+        raise ValueError("degenerate root cell")
+    two = max([D.denominator] + [v.denominator for row in P for v in row])
+    Pi, Di = [[int(v * two) for v in row] for row in P], int(D * two)
+    s = degree
+    assert 2 * s + 1 >= 2 * degree
+    nd = len(_basis_numerators([0] * (d + 1), 1, d, degree))
+    T = [[F(0)] * (2 * nd) for _ in range(2 * nd)]
+    for den, w, pts in gm_rule(d, s):
+        Q = (den, den * Di)
+        S = [[0] * (2 * nd) for _ in range(2 * nd)]
+        for p in pts:
+            nr = [sum(p[v] * Pi[v][k] for v in range(d + 1)) for k in range(d + 1)]
+            M = _basis_numerators(list(p), Q[0], d, degree) + [-v for v in _basis_numerators(nr, Q[1], d, degree)]
+            for i in range(2 * nd):
+                if M[i]:
+                    Si, Mi = S[i], M[i]
+                    for j in range(i, 2 * nd):
+                        Si[j] += Mi * M[j]
+        for i in range(2 * nd):
+            for j in range(i, 2 * nd):
+                if S[i][j]:
+                    T[i][j] += w * F(S[i][j], (Q[i >= nd] * Q[j >= nd]) ** degree)
+    vol = abs(det([[F(1)] + list(r) for r in Xb])) / math.factorial(d)
+    scale = vol * F(beta)
+    for i in range(2 * nd):
+        for j in range(i, 2 * nd):
+            T[i][j] = T[j][i] = scale * T[i][j]
+    return T
+
+
+def pair_tensor(x, conn, tdim, degree, bad, root, beta, bs=1, dtype=np.float64):
+    """beta int_{K_bad} M_i M_j, M = [N_bad, -(N_root o F_root^-1)], as the (2 ND bs)^2 macro tensor of an
+    interior-facet-type entity (include/cutfemx_amd.h): [[00, 01], [10, 11]], (dof i, component a) at i * bs + a, equal
+    components only.  Fractions of the float64 inputs (beta included) until the one rounding through `_ld`."""
+    T = np.array([[_ld(v) for v in row] for row in pair_tensor_exact(x, conn, tdim, degree, bad, root, F(float(beta)))], dtype=LD)
+    return (T if bs == 1 else np.kron(T, np.eye(bs, dtype=LD))).astype(dtype)
+
+
+def unit_pair_tensor(key, cs, degree, bad, root):
+    """The scalar pair block with beta = 1 in longdouble, cached per pair."""
+    return cached(("pair", key, degree, int(bad), int(root)),
+                  lambda: pair_tensor(cs["x"], cs["conn"], cs["tdim"], degree, int(bad), int(root), 1.0, dtype=LD))
+
+
+def pair_block_scales(T, nd):
+    """sqrt(max|T_aa| max|T_bb|) for the four blocks (a, b) of a macro tensor with nd rows per cell: the block-wise scale
+    of a pair comparison (for a far pair the root x root block is 10^4 to 10^5 times the bad x bad one)."""
+    A = np.abs(np.asarray(T, dtype=np.float64))
+    top = [A[:nd, :nd].max(), A[nd:, nd:].max()]
+    S = np.empty_like(A)
+    for a in (0, 1):
+        for b in (0, 1):
+            S[a * nd:(a + 1) * nd, b * nd:(b + 1) * nd] = math.sqrt(top[a] * top[b])
+    return S
+
+
+def exact_pair_entries(key, cs, dofmap, bs, degree, pairs, beta, beta_cell=None):
+    """(rows, cols, values, scales) of the assembled pair form, one entry per (row, column), rows then columns
+    ascending: values = the sum of beta (x beta_cell[bad]) x the exact pair blocks scattered with the blocked dofmap of
+    (bad, root), accumulated in longdouble and rounded once; scales = the sum of the absolute values of the same
+    contributions.  An entry all of whose contributions are exactly zero (the P2 mass of a vertex and an adjacent edge
+    function in the bad x bad block) has no such scale: there the scale is the sum of the block scales of
+    `pair_block_scales`, which is what the comparison of the pair tensors themselves allows those entries."""
+    pairs = np.asarray(pairs).reshape(-1, 4)
+    bc = None if beta_cell is None else np.ascontiguousarray(beta_cell, dtype=np.float64)
+
+    def run():
+        nd = np.asarray(dofmap).shape[1]
+        n = 2 * nd
+        R, Cc, Vv, Zz = [], [], [], []
+        for bad, _, root, _ in pairs.tolist():
+            T = unit_pair_tensor(key, cs, degree, bad, root) * (LD(beta) * (LD(1) if bc is None else LD(bc[bad])))
+            dofs = np.concatenate([dofmap[bad], dofmap[root]]).astype(np.int64)
+            R.append(np.repeat(dofs, n)); Cc.append(np.tile(dofs, n)); Vv.append(T.ravel())
+            Zz.append(np.where(T == 0, pair_block_scales(T, nd), 0.0).ravel())
+        if not R:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), np.zeros(0)
+        r, c, v, z = np.concatenate(R), np.concatenate(Cc), np.concatenate(Vv), np.concatenate(Zz)
+        order = np.lexsort((c, r))
+        r, c, v, z = r[order], c[order], v[order], z[order]
+        first = np.flatnonzero(np.r_[True, (r[1:] != r[:-1]) | (c[1:] != c[:-1])])
+        s = np.add.reduceat(np.abs(v), first).astype(np.float64)
+        r, c, v = r[first], c[first], np.add.reduceat(v, first).astype(np.float64)
+        s = np.where(s > 0, s, np.add.reduceat(z, first))
+        # (dof i, component a) at i * bs + a, equal components only; rows then columns ascending again
+        r, c = (r[:, None] * bs + np.arange(bs)).ravel(), (c[:, None] * bs + np.arange(bs)).ravel()
+        v, s = np.repeat(v, bs), np.repeat(s, bs)
+        order = np.lexsort((c, r))
+        return r[order], c[order], v[order], s[order]
+    tag = ("pentries", key, degree, bs, float(beta), None if bc is None else bc.tobytes(), pairs.tobytes(),
+           np.ascontiguousarray(dofmap, dtype=np.int64).tobytes())
+    return cached(tag, run)
+
+
+def exact_fraction(cs, c, selector):
+    """Volume of the selector's part of cell c over the cell's volume, as a Fraction (0 <= . <= 1)."""
+    ph = cell_phi(cs.get("phis", [cs["phi"]]), cs["conn"][c])
+    return sum((volfrac(leaf) for leaf in region(cs["tdim"], [(ph[k], s) for k, s in parse(selector)])), F(0))
+
+
+def exact_fractions(key, cs, selector):
+    """`exact_fraction` of every cut cell of the case as float64 (each rounded once), cached."""
+    sel = selector.replace(" ", "")
+    return cached(("fractions", key, sel), lambda: np.array([float(exact_fraction(cs, c, sel)) for c in cs["cut"]]))
+
+
+def shared_vertices(conn, pairs):
+    """Number of vertices the two cells of each pair share."""
+    pairs = np.asarray(pairs).reshape(-1, 4)
+    return np.array([len(set(conn[b].tolist()) & set(conn[r].tolist())) for b, r in pairs[:, [0, 2]].tolist()], dtype=np.int64)
+
+
+def longest_pair_row(dofmap, bs, pairs, ndofs):
+    """Longest row (in scalar columns) of the pair form's sparsity with the all-rows diagonal, from pairs and dofmap."""
+    import scipy.sparse as sp
+    pairs = np.asarray(pairs).reshape(-1, 4)
+    dm = np.asarray(dofmap, dtype=np.int64)
+    macro = np.concatenate([dm[pairs[:, 0]], dm[pairs[:, 2]]], axis=1)
+    n = macro.shape[1]
+    r, c = np.repeat(macro, n, axis=1).ravel(), np.tile(macro, (1, n)).ravel()
+    r, c = np.concatenate([r, np.arange(ndofs)]), np.concatenate([c, np.arange(ndofs)])
+    A = sp.coo_matrix((np.ones(r.size), (r, c)), shape=(ndofs, ndofs)).tocsr()
+    return int(np.diff(A.indptr).max()) * bs
