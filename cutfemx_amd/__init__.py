@@ -8,6 +8,7 @@ package needs no GPU, calling into it does.
 """
 from . import fem
 from . import extensions
+from . import distance
 from .cut import (CutData, FacetRows, RuntimeQuadratureRules, cut, exterior_facets, full_cell_rules, full_facet_rules,
                   ghost_penalty_facets, interior_facets_for_cells,
                   level_set_value, locate_entities, locate_entities_device, normal, runtime_quadrature,
@@ -19,6 +20,6 @@ __all__ = [
     "CutData", "FacetRows", "RuntimeQuadratureRules", "cut", "update", "locate_entities",
     "locate_entities_device", "runtime_quadrature", "runtime_quadratures", "full_cell_rules",
     "ghost_penalty_facets", "interior_facets_for_cells", "exterior_facets", "full_facet_rules", "normal", "level_set_value", "Mesh", "FunctionSpace", "Function",
-    "box_mesh_arrays", "box_lagrange2_dofmap", "lagrange_dofmap", "fem", "extensions",
+    "box_mesh_arrays", "box_lagrange2_dofmap", "lagrange_dofmap", "fem", "extensions", "distance",
     "step", "run_step", "set_step_margin", "forget_step_history",
 ]

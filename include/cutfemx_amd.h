@@ -744,6 +744,59 @@ int cfx_minres_solve(int64_t nrows, const int64_t* indptr, const int32_t* indice
                      const int32_t* rows, int64_t n_rows, const double* b, double* x /* in: x0, out: x */,
                      const cfx_minres_options* opt /* or NULL: the defaults */, cfx_cg_info* info /* host or device pointer */);
 
+/* ---- reinitialisation: a P1 level set back to a signed distance function, in HBM ----------------------------------
+ * cutfemx.distance.reinitialize(phi, max_iter, tol) of the reference (cpp/cutfemx/distance/reinitialize.h:490-575,
+ * fast_iterative.h:146-468, eikonal_update.h; python/cutfemx/distance.py:154-160): the stage a moving-domain loop runs
+ * between steps.  V must be scalar, of degree 1 and on the geometry dofmap; phi (one double per vertex, host or device)
+ * is overwritten in place.
+ *   sign        s_v = +1 where phi_v >= 0, else -1 (reinitialize.h:505-510)
+ *   near field  an edge (i, j) of a cell is crossed when (phi_i < 0) != (phi_j < 0), at
+ *               p_ij = x_i + phi_i / (phi_i - phi_j) (x_j - x_i); a cell with a crossed edge is a seed cell, its piece G_K
+ *               the convex hull of its crossing points (a segment; a triangle or a planar quadrilateral);
+ *               d0_v = min over the seed cells K around v of dist(x_v, G_K); phi_v == 0 gives d0_v = 0; every other
+ *               vertex starts at inf_value (init_nearfield_from_surface, reinitialize.h:353-394, without the cut mesh)
+ *   update      U(t, K) = min over y in conv{x_s : s in K \ {t}, d_s finite} of (interpolated d)(y) + |x_t - y|: the
+ *               least of update_1pt / update_2pt / update_3pt over the finite sub-faces (fast_iterative.h:282-377)
+ *   iteration   d_t <- min(d_t, min over the cells K around t of U(t, K)), from d0 until nothing changes
+ *   result      phi_v <- s_v d_v; an exact zero stays +0.0; a vertex never reached gets s_v min(inf_value, max_distance)
+ * The iteration is monotone: its limit does not depend on the order of the updates.  The engine runs Jacobi-type
+ * sweeps over the list of vertices next to a change.  Two calls on the same inputs give the same bits.
+ * Deviations from the reference, on purpose: the 3-point update is the closed form (the larger root of the quadratic of
+ * the face's Gram matrix, valid while its multipliers are <= 0) instead of a 20-step Newton iteration
+ * (eikonal_update.h:157-255); a face is degenerate relative to its own size (eikonal_update.h:144 tests |cross|^2 <
+ * 1e-14); an improvement is accepted when it is strict (new < old), without the reference's absolute 1e-13 slack.
+ * max_distance = B > 0 (the one extension): a value is used as a source, and activates its neighbours, only while it
+ * is <= B, and the output is clamped to B -- the result is where(d <= B, d, B) of the unbanded one after about B / h
+ * sweeps instead of (largest distance) / h.
+ * max_iter counts sweeps (about 1.3 x largest distance / h are needed); tol is kept for the reference's signature:
+ * "converged" means that the list of vertices to update is empty (what fast_iterative.h:454 reduces to).
+ *   CFX_REINIT_CONVERGED     the list ran empty after info.sweeps sweeps
+ *   CFX_REINIT_MAX_ITER      max_iter sweeps were made: phi is written, an upper bound of the distance everywhere
+ *   CFX_REINIT_NO_INTERFACE  no crossed edge and no zero: phi is left untouched, bit for bit
+ * info: sweeps that had vertices to update, seed vertices (finite d0), vertex updates computed -- counted on the device.
+ * check_every: the host reads the list length every check_every sweeps and stops launching once it is 0; a sweep
+ * launched on an empty list does nothing, so phi and info do not depend on it.  check_every = 0 launches exactly
+ * max_iter sweeps; with a DEVICE phi and a DEVICE (or NULL) info the call then makes no host round trip
+ * (cfx_sync_count does not grow): it may run between cfx_step_begin and cfx_step_end, in front of cfx_cut_update on
+ * the same device pointer. */
+#define CFX_REINIT_CONVERGED 1
+#define CFX_REINIT_MAX_ITER 2
+#define CFX_REINIT_NO_INTERFACE 3
+typedef struct
+{
+  double tol, inf_value, max_distance /* <= 0: none */;
+  int32_t max_iter, check_every;
+} cfx_reinit_options;
+typedef struct
+{
+  int32_t reason, sweeps;
+  int64_t seeds, updates;
+} cfx_reinit_info;
+int cfx_reinit_options_default(cfx_reinit_options* opt); /* tol 1e-10, inf_value 1e30, max_distance 0, max_iter 1000,
+                                                            check_every 8; works without a GPU */
+int cfx_reinitialize(cfx_space_t V, double* phi /* host or device, in place */,
+                     const cfx_reinit_options* opt /* or NULL: the defaults */, cfx_reinit_info* info /* host or device, or NULL */);
+
 /* ---- float32 instantiation of the boundary --------------------------------------------------------------
  * python/cutfemx/wrappers/fem.cpp:490-500 declares the runtime assembly for <T, U> in {float, double}^2 and
  * wrappers/cut.cpp:403-407 the cut API for float and double: T = scalar type of MatrixCSR / Vector / Function,

@@ -842,4 +842,33 @@ inline CellAggregation create_cell_aggregation(const CutData& cut_data, std::str
   return a;
 }
 } // namespace extensions
+
+namespace distance
+{
+/// cfx_reinit_options with the library's defaults (tol 1e-10, inf_value 1e30, no band, 1000 sweeps, check_every 8)
+struct ReinitOptions : cfx_reinit_options
+{
+  ReinitOptions() { check(cfx_reinit_options_default(this)); }
+};
+
+/// cutfemx::distance::reinitialize (cpp/cutfemx/distance/reinitialize.h:490-575): the P1 level set `phi` on `V` -- scalar,
+/// degree 1, on the geometry dofmap -- becomes the signed distance to its own zero contour, in place, in HBM
+/// (cfx_reinitialize).  Signs and exact zeros are kept; options.max_distance > 0 computes a band and clamps the rest.
+/// Every reason (converged, max_iter, no interface) is returned in the info; only bad arguments throw.
+inline cfx_reinit_info reinitialize(const fem::FunctionSpace& V, std::span<double> phi,
+                                    const cfx_reinit_options& options = ReinitOptions())
+{
+  if ((std::int64_t)phi.size() != V.ndofs * V.bs) throw std::invalid_argument("reinitialize: one value of phi per dof");
+  cfx_reinit_info info{};
+  check(cfx_reinitialize(V.handle.h, phi.data(), &options, &info));
+  return info;
+}
+/// ... with a raw pointer (host or device) and the cfx_reinit_info left in HBM (`device_info`, or nullptr): with a
+/// device `phi` and options.check_every = 0 the call makes no host round trip
+inline void reinitialize(const fem::FunctionSpace& V, double* phi, const cfx_reinit_options& options,
+                         cfx_reinit_info* device_info)
+{
+  check(cfx_reinitialize(V.handle.h, phi, &options, device_info));
+}
+} // namespace distance
 } // namespace cutfemx_amd
