@@ -811,10 +811,18 @@ struct cfx_mesh_s
   // ... and of its kClassSub quarter blocks (kClassSubRuns runs each): a block with vertices on both sides is decided
   // quarter by quarter before any cell is looked at
   cfx::DevArray<int2> class_sub_runs; // [nblocks * kClassSub * kClassSubRuns]
+  // ... and, from the runs, the aligned 16 B words of a sign-code array that the block's vertices lie in: kClassChunks
+  // descriptors (x: index of the word, y: bit i set when byte i of the word belongs to a run; unused slots 0, 0) per
+  // block, the blocks padded to an even number.  y = -1 in slot 0: the block has no summary or more words than slots,
+  // and is decided from its runs.  The block decision loads the words whole (classify_culled_kernel).
+  cfx::DevArray<int2> class_chunks;   // [(nblocks rounded up to even) * kClassChunks]
   bool class_built = false;
 };
 constexpr int kClassBlock = 1024, kClassRuns = 32; // (one wavefront classifies a block: 16 cells per lane)
 constexpr int kClassSub = 4, kClassSubRuns = 16;
+constexpr int kClassChunks = 64; // (two descriptors per lane of a half wavefront: 512 B per block)
+// bytes of a sign-code array of n dofs: whole 16 B words, so that a word the last dofs lie in can be loaded whole
+inline int64_t class_code_bytes(int64_t n) { return (n + 15) & ~int64_t(15); }
 
 struct cfx_rules_s
 {

@@ -390,6 +390,51 @@ __global__ void __launch_bounds__(kBlock) class_summary_kernel(int64_t ncells, c
   }
 }
 
+// The chunk descriptors of a block (cfx_mesh_s::class_chunks) from its runs, one wavefront per block: the aligned 16 B
+// words of a sign-code array that the runs touch, ascending, each with the mask of its bytes that belong to a run.  The
+// runs ascend and are at least one id apart, so a word is shared by neighbouring runs only: run j opens the words from
+// its first to its last, less the first when run j - 1 ended in it (several short runs may lie in one word).  More than
+// kClassChunks words, or no summary: -1 in the mask of slot 0.  Blocks from nblocks on (the padding to an even number)
+// get empty descriptors.
+__global__ void __launch_bounds__(kBlock) class_chunks_kernel(int64_t nblocks, int64_t nblocks_padded, const int2* __restrict__ runs,
+                                                              int2* __restrict__ chunks)
+{
+  static_assert(kClassChunks == 64 && kClassRuns <= 64, "one descriptor and at most one run per lane");
+  __shared__ int32_t s_word[kBlock / 64][kClassChunks];
+  __shared__ uint32_t s_mask[kBlock / 64][kClassChunks];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * (kBlock / 64) + w;
+  const bool real = b < nblocks;
+  int2 r = make_int2(0, 0);
+  if (real && lane < kClassRuns) r = runs[b * kClassRuns + lane];
+  const bool summary = real && __shfl(r.y, 0, 64) >= 0;
+  const bool have = summary && r.y > 0;
+  const int wlo = r.x >> 4, whi = (r.x + (have ? r.y - 1 : 0)) >> 4;
+  const int prev_hi = __shfl_up(whi, 1, 64);
+  const int first_new = wlo + ((have && lane > 0 && prev_hi == wlo) ? 1 : 0);
+  const int cnt = have ? whi - first_new + 1 : 0;
+  const int incl = wave_inclusive_scan<int>(cnt);
+  const int total = __shfl(incl, 63, 64);
+  const int off = incl - cnt;
+  const bool fits = summary && total <= kClassChunks;
+  s_word[w][lane] = 0; s_mask[w][lane] = 0u;
+  __syncthreads();
+  if (fits && have)
+  {
+    for (int k = 0; k < cnt; ++k) s_word[w][off + k] = first_new + k;
+    for (int wd = wlo; wd <= whi; ++wd)
+    {
+      const int slot = off + (wd - first_new); // (off - 1: the word the run before ended in)
+      const int lo = wd == wlo ? (r.x & 15) : 0, hi = wd == whi ? ((r.x + r.y - 1) & 15) + 1 : 16;
+      atomicOr(&s_mask[w][slot], ((1u << hi) - 1u) & ~((1u << lo) - 1u));
+    }
+  }
+  __syncthreads();
+  int2 d = make_int2(s_word[w][lane], (int)s_mask[w][lane]);
+  if (!fits) d = make_int2(0, (real && lane == 0) ? -1 : 0);
+  if (b < nblocks_padded) chunks[b * kClassChunks + lane] = d;
+}
+
 // AND of the sign codes of the vertices a run table lists (RUNS slots of (start, length), one per lane; length 0: unused,
 // -1 in slot 0: no summary -> 0).  The elements are numbered through (prefix sums of the lengths) and dealt to the lanes E
 // at a time, so that a lane's loads are independent and in flight together: walking the runs one after the other left
@@ -436,7 +481,10 @@ __device__ __forceinline__ void class_fill(int8_t* __restrict__ domain, int64_t 
   const uint32_t w4 = 0x01010101u * (uint32_t)(uint8_t)d;
   // 16 B per lane when the run is whole and aligned: one store instruction per 1024 cells.  (The kernel is not bound by
   // its stores -- 0.78 -> 0.75 ms with every block uniform -- nor helped by a persistent grid with the next block's
-  // runs prefetched: 1.5 ms; 786 k short wavefronts live on how many of them are in flight.)
+  // runs prefetched: 1.5 ms.  Round 5 read that as "786 k short wavefronts live on how many of them are in flight";
+  // round 12 found the other half: the wavefronts were not short.  Decoding the runs cost ~1200 issued instructions per
+  // pair of blocks, and with the decode gone -- class_chunks_and2 -- the all-uniform case went from 0.51 to 0.26 ms at
+  // 512^3, the time its bytes take at the rate fill16_kernel streams at.)
   if (cbase + CELLS <= ncells && (reinterpret_cast<uintptr_t>(domain + cbase) & 15) == 0)
   {
     if (lane < CELLS / 16) reinterpret_cast<uint4*>(domain + cbase)[lane] = make_uint4(w4, w4, w4, w4);
@@ -453,9 +501,11 @@ __device__ __forceinline__ void class_fill(int8_t* __restrict__ domain, int64_t 
 }
 
 // The same for TWO tables at once (lanes 0..31 hold the runs of table A, lanes 32..63 those of table B; RUNS <= 32): both
-// tables arrive with one load latency and both sets of sign codes with a second one.  The culled classification is
-// bound by how many of its short wavefronts are in flight (786 k of them at 512^3, two dependent loads each): a
-// wavefront that decides two blocks halves their number.
+// tables arrive with one load latency and both sets of sign codes with a second one: a wavefront that decides two
+// blocks halves the number of wavefronts (786 k at 512^3, two dependent loads each).  What this decoder costs beside
+// its loads -- a scan, and per run and address a compare-and-select chain in a loop the compiler treats as divergent --
+// is repeated every step for runs that never change: it is the path of CFX_CLASSIFY_CHUNKS=0 and of code arrays that
+// are not 16 B aligned now; class_chunks_and2 reads the same bytes through a table built once per mesh.
 template <int RUNS, int E>
 __device__ __forceinline__ void class_runs_and2(const int2* __restrict__ tableA, const int2* __restrict__ tableB, bool haveB,
                                                 const uint8_t* __restrict__ code, int lane, unsigned& allA, unsigned& allB)
@@ -503,15 +553,130 @@ __device__ __forceinline__ void class_runs_and2(const int2* __restrict__ tableA,
   for (int o = 32; o > 0; o >>= 1) { allA &= __shfl_xor(allA, o, 64); allB &= __shfl_xor(allB, o, 64); }
 }
 
-// a block with vertices on both sides (or on the interface): quarter by quarter, and only the quarters that are mixed
-// themselves cell by cell (classify_kernel).  The whole wavefront works on the one block.
-template <int ND>
+// AND of the bytes of a 16 B word of sign codes whose bit is set in mask (bit i: byte i); the other bytes count as 0xff.
+// (nibble -> byte mask: the four shifted copies of the nibble do not overlap, so bit k lands alone at bit 8 k)
+__device__ __forceinline__ unsigned class_word_and(const uint4 w, unsigned mask)
+{
+  auto keep = [](unsigned v, unsigned nib) { return v | ~((((nib & 15u) * 0x00204081u) & 0x01010101u) * 0xffu); };
+  unsigned a = keep(w.x, mask) & keep(w.y, mask >> 4) & keep(w.z, mask >> 8) & keep(w.w, mask >> 12);
+  a &= a >> 16;
+  return a & (a >> 8);
+}
+
+// The block decision of a pair of blocks from their chunk descriptors (cfx_mesh_s::class_chunks: mesh-static, where the
+// run tables had to be scanned and decoded into byte addresses by every wavefront of every step): one 16 B load of two
+// descriptors per lane -- lanes 0..31 those of block A, 32..63 those of block B, 1 KB of one stream --, two 16 B loads of
+// sign codes per lane (an unused descriptor names word 0 with an empty mask: no branch around the load), the masked
+// AND, and two ballots for the reduction over each half.  Exactly the bytes of the runs take part, as in
+// class_runs_and2.  A flagged block (no summary, or more than kClassChunks words) takes the run decoder.
+// code starts on a 16 B boundary and its allocation covers whole words (checked at the launch).
+template <int RUNS, int E>
+__device__ __forceinline__ void class_chunks_and2(const int2* __restrict__ chunks, const int2* __restrict__ tableA, bool haveB,
+                                                  const uint8_t* __restrict__ code, int lane, unsigned& allA, unsigned& allB)
+{
+  const int4 d = reinterpret_cast<const int4*>(chunks)[lane];
+  const bool flagA = __builtin_amdgcn_readlane(d.y, 0) < 0, flagB = haveB && __builtin_amdgcn_readlane(d.y, 32) < 0;
+  const uint4* __restrict__ words = reinterpret_cast<const uint4*>(code);
+  const uint4 w0 = words[d.x], w1 = words[d.z];
+  const unsigned acc = class_word_and(w0, (unsigned)d.y) & class_word_and(w1, (unsigned)d.w);
+  const unsigned long long no1 = __ballot((acc & 1u) == 0u), no2 = __ballot((acc & 2u) == 0u);
+  allA = ((no1 & 0xffffffffull) == 0 ? 1u : 0u) | ((no2 & 0xffffffffull) == 0 ? 2u : 0u);
+  allB = ((no1 >> 32) == 0 ? 1u : 0u) | ((no2 >> 32) == 0 ? 2u : 0u);
+  if (flagA) allA = class_runs_and<RUNS, E>(tableA, code, lane);
+  if (flagB) allB = class_runs_and<RUNS, E>(tableA + RUNS, code, lane);
+}
+
+// AND of the sign codes over the 16 B words that the spans of a quarter table lie in (kClassSubRuns spans, four lanes per
+// span, a word per lane and round: spans of up to 64 ids in one round).  The spans are supersets of the quarter's
+// vertices already, so the bytes of their first and last word that lie outside them take part as well: a quarter they
+// turn mixed goes cell by cell, which gives the same cells the same classes.  Pad bytes behind the last dof likewise.
+// code starts on a 16 B boundary and its allocation covers whole words (checked at the launch).
+__device__ __forceinline__ unsigned class_spans_and_words(const int2* __restrict__ table, const uint8_t* __restrict__ code, int lane)
+{
+  static_assert(kClassSubRuns * 4 == 64, "four lanes per span");
+  const int2 s = table[lane >> 2];
+  if (__builtin_amdgcn_readlane(s.y, 0) < 0) return 0u; // no summary
+  const uint4* __restrict__ words = reinterpret_cast<const uint4*>(code);
+  const int last = s.y > 0 ? (s.x + s.y - 1) >> 4 : -1;
+  unsigned acc = 0xffffffffu;
+  for (int w = (s.x >> 4) + (lane & 3); __any(w <= last); w += 4)
+    if (w <= last)
+    {
+      const uint4 v = words[w];
+      acc &= v.x & v.y & v.z & v.w;
+    }
+  acc &= acc >> 16;
+  acc &= acc >> 8;
+  const unsigned long long no1 = __ballot((acc & 1u) == 0u), no2 = __ballot((acc & 2u) == 0u);
+  return (no1 == 0 ? 1u : 0u) | (no2 == 0 ? 2u : 0u);
+}
+
+// one quarter of a block with vertices on both sides (or on the interface): decided whole from its table where its
+// vertices have one sign, cell by cell (classify_kernel) otherwise.  The whole wavefront works on the one quarter; n_in
+// and n_cut take its inside / cut cells, spread over the lanes.  (WORDS: the decision from whole 16 B words, as the
+// block's own from its chunk descriptors; otherwise from the run decoder.)
+template <int ND, bool WORDS>
+__device__ __forceinline__ void classify_quarter(int64_t ncells, int64_t b, int sq, const int32_t* __restrict__ dofmap,
+                                                 const int2* __restrict__ sub_runs, const uint8_t* __restrict__ code,
+                                                 int8_t* __restrict__ domain, uint8_t* __restrict__ touch, int lane, int& n_in, int& n_cut)
+{
+  constexpr int SUB = kClassBlock / kClassSub, U = SUB / 64;
+  const int64_t sbase = b * kClassBlock + (int64_t)sq * SUB;
+  const int2* table = sub_runs + (b * kClassSub + sq) * kClassSubRuns;
+  unsigned sall;
+  if constexpr (WORDS) sall = class_spans_and_words(table, code, lane);
+  else sall = class_runs_and<kClassSubRuns, 4>(table, code, lane);
+  if (sall == 1u || sall == 2u)
+  {
+    class_fill<SUB>(domain, sbase, ncells, sall == 1u ? (int8_t)CFX_INSIDE : (int8_t)CFX_OUTSIDE, lane);
+    if (sall == 1u && lane == 0) n_in += (int)(ncells - sbase < SUB ? ncells - sbase : SUB);
+    return;
+  }
+  int32_t d[U][ND];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+  {
+    const int64_t c = sbase + lane + (int64_t)u * 64;
+    if (c >= ncells) continue;
+    if constexpr (ND == 4)
+    {
+      const int4 v = *reinterpret_cast<const int4*>(dofmap + c * 4);
+      d[u][0] = v.x; d[u][1] = v.y; d[u][2] = v.z; d[u][3] = v.w;
+    }
+    else
+    {
+#pragma unroll
+      for (int i = 0; i < ND; ++i) d[u][i] = dofmap[c * ND + i];
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+  {
+    const int64_t c = sbase + lane + (int64_t)u * 64;
+    if (c >= ncells) continue;
+    unsigned a = 3u;
+#pragma unroll
+    for (int i = 0; i < ND; ++i) a &= code[d[u][i]];
+    domain[c] = a == 1u ? (int8_t)CFX_INSIDE : (a == 2u ? (int8_t)CFX_OUTSIDE : (int8_t)CFX_INTERSECTED);
+    n_in += a == 1u ? 1 : 0;
+    n_cut += (a != 1u && a != 2u) ? 1 : 0;
+    if (touch && a != 1u && a != 2u) // (a cut cell: its dofs are next to the interface; every writer stores 1)
+    {
+#pragma unroll
+      for (int i = 0; i < ND; ++i) touch[d[u][i]] = 1;
+    }
+  }
+}
+
+// a block with vertices on both sides (or on the interface): quarter by quarter.  The whole wavefront works on the one
+// block.
+template <int ND, bool WORDS>
 __device__ __forceinline__ void classify_block_mixed(int64_t ncells, int64_t b, const int32_t* __restrict__ dofmap,
                                                      const int2* __restrict__ sub_runs, const uint8_t* __restrict__ code,
                                                      int8_t* __restrict__ domain, int32_t* tiles_inside, int32_t* tiles_cut,
                                                      uint8_t* __restrict__ touch, int lane)
 {
-  constexpr int SUB = kClassBlock / kClassSub, U = SUB / 64;
+  constexpr int SUB = kClassBlock / kClassSub;
   const int64_t cbase = b * kClassBlock;
   const int64_t tile = cbase / kByteTile;
   int n_in = 0, n_cut = 0;
@@ -519,49 +684,8 @@ __device__ __forceinline__ void classify_block_mixed(int64_t ncells, int64_t b, 
   // 1.056 against 1.044 ms at 512^3: the mixed blocks live on their cell loops)
   for (int sq = 0; sq < kClassSub; ++sq)
   {
-    const int64_t sbase = cbase + (int64_t)sq * SUB;
-    if (sbase >= ncells) break;
-    const unsigned sall = class_runs_and<kClassSubRuns, 4>(sub_runs + (b * kClassSub + sq) * kClassSubRuns, code, lane);
-    if (sall == 1u || sall == 2u)
-    {
-      class_fill<SUB>(domain, sbase, ncells, sall == 1u ? (int8_t)CFX_INSIDE : (int8_t)CFX_OUTSIDE, lane);
-      if (sall == 1u && lane == 0) n_in += (int)(ncells - sbase < SUB ? ncells - sbase : SUB);
-      continue;
-    }
-    int32_t d[U][ND];
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-    {
-      const int64_t c = sbase + lane + (int64_t)u * 64;
-      if (c >= ncells) continue;
-      if constexpr (ND == 4)
-      {
-        const int4 v = *reinterpret_cast<const int4*>(dofmap + c * 4);
-        d[u][0] = v.x; d[u][1] = v.y; d[u][2] = v.z; d[u][3] = v.w;
-      }
-      else
-      {
-#pragma unroll
-        for (int i = 0; i < ND; ++i) d[u][i] = dofmap[c * ND + i];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-    {
-      const int64_t c = sbase + lane + (int64_t)u * 64;
-      if (c >= ncells) continue;
-      unsigned a = 3u;
-#pragma unroll
-      for (int i = 0; i < ND; ++i) a &= code[d[u][i]];
-      domain[c] = a == 1u ? (int8_t)CFX_INSIDE : (a == 2u ? (int8_t)CFX_OUTSIDE : (int8_t)CFX_INTERSECTED);
-      n_in += a == 1u ? 1 : 0;
-      n_cut += (a != 1u && a != 2u) ? 1 : 0;
-      if (touch && a != 1u && a != 2u) // (a cut cell: its dofs are next to the interface; every writer stores 1)
-      {
-#pragma unroll
-        for (int i = 0; i < ND; ++i) touch[d[u][i]] = 1;
-      }
-    }
+    if (cbase + (int64_t)sq * SUB >= ncells) break;
+    classify_quarter<ND, WORDS>(ncells, b, sq, dofmap, sub_runs, code, domain, touch, lane, n_in, n_cut);
   }
   if (tiles_inside)
   {
@@ -582,9 +706,11 @@ __device__ __forceinline__ void classify_block_mixed(int64_t ncells, int64_t b, 
 #ifndef CFX_CLASSIFY_E
 #define CFX_CLASSIFY_E 12 // sign codes per lane, table and round of loads (a block has ~690: one round)
 #endif
-template <int ND>
+// (CHUNKS: the block decision from the chunk descriptors; otherwise, and for the blocks the descriptors flag, from the runs)
+template <int ND, bool CHUNKS>
 __global__ void __launch_bounds__(kBlock, CFX_CLASSIFY_WAVES) classify_culled_kernel(int64_t ncells, int64_t nblocks, const int32_t* __restrict__ dofmap,
-                                                                 const int2* __restrict__ runs, const int2* __restrict__ sub_runs,
+                                                                 const int2* __restrict__ runs, const int2* __restrict__ chunks,
+                                                                 const int2* __restrict__ sub_runs,
                                                                  const uint8_t* __restrict__ code, int8_t* __restrict__ domain,
                                                                  int32_t* tiles_inside, int32_t* tiles_cut,
                                                                  uint8_t* __restrict__ block_class, uint8_t* __restrict__ touch)
@@ -595,7 +721,10 @@ __global__ void __launch_bounds__(kBlock, CFX_CLASSIFY_WAVES) classify_culled_ke
   if (b0 >= nblocks) return;
   const bool have1 = b0 + 1 < nblocks;
   unsigned all[2];
-  class_runs_and2<kClassRuns, CFX_CLASSIFY_E>(runs + b0 * kClassRuns, runs + (b0 + 1) * kClassRuns, have1, code, lane, all[0], all[1]);
+  if constexpr (CHUNKS)
+    class_chunks_and2<kClassRuns, CFX_CLASSIFY_E>(chunks + b0 * kClassChunks, runs + b0 * kClassRuns, have1, code, lane, all[0], all[1]);
+  else
+    class_runs_and2<kClassRuns, CFX_CLASSIFY_E>(runs + b0 * kClassRuns, runs + (b0 + 1) * kClassRuns, have1, code, lane, all[0], all[1]);
   for (int k = 0; k < (have1 ? 2 : 1); ++k)
   {
     const int64_t b = b0 + k;
@@ -611,7 +740,7 @@ __global__ void __launch_bounds__(kBlock, CFX_CLASSIFY_WAVES) classify_culled_ke
       continue;
     }
     if (block_class && lane == 0) block_class[b] = 0;
-    classify_block_mixed<ND>(ncells, b, dofmap, sub_runs, code, domain, tiles_inside, tiles_cut, touch, lane);
+    classify_block_mixed<ND, CHUNKS>(ncells, b, dofmap, sub_runs, code, domain, tiles_inside, tiles_cut, touch, lane);
   }
 }
 
@@ -2378,8 +2507,12 @@ void classify(cfx_cut_t cut)
     // ... next to one byte per level-set dof that the classification sets on the dofs of every cut cell: a dof with
     // a negative (positive) value and no cut cell around it has only inside (outside) cells around it)
     DevArray<uint8_t> codes_k;
-    if (k == 0 && cut->codes0.n != cut->ls_ndofs) { cut->codes0.alloc(cut->ls_ndofs); cut->touch0.alloc(cut->ls_ndofs); }
-    if (k != 0) codes_k.alloc(cut->ls_ndofs);
+    // (allocated in whole 16 B words: the block decision loads the words the last dofs lie in.  The pad bytes are never
+    // written; no descriptor's mask names them, so they take no part in a block's decision.  A quarter's decision ANDs
+    // whole words and may meet them: whatever they hold can only send a uniform quarter cell by cell, class_spans_and_words)
+    const int64_t code_bytes = class_code_bytes(cut->ls_ndofs);
+    if (k == 0 && cut->codes0.n != code_bytes) { cut->codes0.alloc(code_bytes); cut->touch0.alloc(cut->ls_ndofs); }
+    if (k != 0) codes_k.alloc(code_bytes);
     struct { uint8_t* p; } codes{k == 0 ? cut->codes0.p : codes_k.p};
     uint8_t* touch = k == 0 ? cut->touch0.p : nullptr;
     if (k == 0) cut->touch_valid = false;
@@ -2466,8 +2599,27 @@ void classify(cfx_cut_t cut)
         const dim3 cgrid((unsigned)(((nb + 1) / 2 + kBlock / 64 - 1) / (kBlock / 64)));   // a wavefront per pair of blocks
         uint8_t* bclass = nullptr;
         if (k == 0 && t_in != nullptr) { cut->block_class.alloc(nb); bclass = cut->block_class.p; }
-        if (nd == 4) launch("classify", classify_culled_kernel<4>, cgrid, dim3(kBlock), 0, nc, nb, cut->ls_dofmap.p, (const int2*)mesh->class_runs.p, (const int2*)mesh->class_sub_runs.p, phi, dom, t_in, t_cut, bclass, touch);
-        else launch("classify", classify_culled_kernel<3>, cgrid, dim3(kBlock), 0, nc, nb, cut->ls_dofmap.p, (const int2*)mesh->class_runs.p, (const int2*)mesh->class_sub_runs.p, phi, dom, t_in, t_cut, bclass, touch);
+        // the block decision from the mesh-static chunk descriptors (built at the first classification that takes them):
+        // the sign codes are loaded as whole 16 B words, so they start on a 16 B boundary (their allocation covers
+        // whole words: code_bytes above); CFX_CLASSIFY_CHUNKS=0: from the runs
+        const bool chunked = env_on<Sw::CLASSIFY_CHUNKS>() && (reinterpret_cast<uintptr_t>(phi) & 15) == 0;
+        if (chunked && mesh->class_chunks.n == 0)
+        {
+          const int64_t nbp = (nb + 1) & ~int64_t(1);
+          mesh->class_chunks.alloc(nbp * kClassChunks);
+          launch("classify_chunks", class_chunks_kernel, dim3((unsigned)((nbp + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0,
+                 nb, nbp, (const int2*)mesh->class_runs.p, mesh->class_chunks.p);
+          publish_across_lanes();
+        }
+        const int2 *runs = mesh->class_runs.p, *chunks = mesh->class_chunks.p, *sub_runs = mesh->class_sub_runs.p;
+        auto block_pass = [&](auto kernel) {
+          launch("classify", kernel, cgrid, dim3(kBlock), 0, nc, nb, cut->ls_dofmap.p, runs, chunks, sub_runs, phi, dom, t_in, t_cut, bclass,
+                 touch);
+        };
+        if (nd == 4 && chunked) block_pass(classify_culled_kernel<4, true>);
+        else if (nd == 4) block_pass(classify_culled_kernel<4, false>);
+        else if (chunked) block_pass(classify_culled_kernel<3, true>);
+        else block_pass(classify_culled_kernel<3, false>);
         if (k == 0) cut->touch_valid = true;
         continue;
       }
@@ -2703,6 +2855,39 @@ int cfx_cut_domain(cfx_cut_t cut, int ls, const int8_t** domain)
   require(cut && domain, CFX_ERR_INVALID_ARGUMENT, "cfx_cut_domain: null argument");
   require(ls >= 0 && ls < cut->nls, CFX_ERR_OUT_OF_RANGE, "level-set index out of range");
   *domain = cut->domain.p + (int64_t)ls * cut->nhosts();
+  CFX_API_END
+}
+
+namespace
+{
+__global__ void __launch_bounds__(kBlock) count_block_class_kernel(int64_t n, const uint8_t* __restrict__ block_class,
+                                                                   unsigned long long* __restrict__ counts)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const unsigned c = i < n ? (unsigned)block_class[i] : 0u;
+  const unsigned long long inside = __ballot(c == 1u), outside = __ballot(c == 2u);
+  if ((threadIdx.x & 63) == 0)
+  {
+    if (inside) atomicAdd(&counts[0], (unsigned long long)__popcll(inside));
+    if (outside) atomicAdd(&counts[1], (unsigned long long)__popcll(outside));
+  }
+}
+} // namespace
+
+int cfx_cut_uniform_blocks(cfx_cut_t cut, int64_t* n_inside, int64_t* n_outside)
+{
+  CFX_API_BEGIN
+  require(cut && n_inside && n_outside, CFX_ERR_INVALID_ARGUMENT, "cfx_cut_uniform_blocks: null argument");
+  *n_inside = *n_outside = -1;
+  const int64_t nb = cut->block_class.n;
+  if (nb == 0) return CFX_OK;
+  cfx::DevArray<unsigned long long> counts(2);
+  counts.zero();
+  cfx::launch("count_block_class", count_block_class_kernel, cfx::grid_for(nb), dim3(cfx::kBlock), 0, nb,
+              (const uint8_t*)cut->block_class.p, counts.p);
+  unsigned long long a = 0, b = 0;
+  cfx::read_two(counts.p, counts.p + 1, a, b);
+  *n_inside = (int64_t)a; *n_outside = (int64_t)b;
   CFX_API_END
 }
 

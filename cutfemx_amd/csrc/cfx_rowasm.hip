@@ -2332,7 +2332,7 @@ cfx_row_plan& row_plan(cfx_form_s* a)
     const ListProvenance* pv = (env_on<Sw::BULK_ROWS>() && one_list && list && (p1 || p2)) ? provenance_lookup(list) : nullptr;
     const int64_t nvert = V->mesh->nnodes;
     if (pv && pv->n == list_n && pv->cut->gen == pv->gen && pv->cut->mesh == V->mesh && pv->cut->ls_dofmap.p == V->mesh->conn.p
-        && pv->cut->ls_ndofs == nvert && pv->cut->codes0.n == nvert && pv->cut->touch_valid && pv->cut->touch0.n == nvert
+        && pv->cut->ls_ndofs == nvert && pv->cut->codes0.n == class_code_bytes(nvert) && pv->cut->touch_valid && pv->cut->touch0.n == nvert
         && (pv->value == -1 || pv->value == 1) && (p1 ? V->ndofs == nvert : space_dof_verts(V)))
     {
       P.bulk = true;

@@ -49,6 +49,7 @@
   CFX_SWITCH(PATTERN_REUSE,      first_char, call,  "0: never copy rows from the space's previous pattern") \
   CFX_SWITCH(IMPLICIT_BOX,       first_char, call,  "1: classification of generated box meshes from the cube index") \
   CFX_SWITCH(CLASSIFY_CULL,      first_char, call,  "0: classification cell by cell instead of block culling") \
+  CFX_SWITCH(CLASSIFY_CHUNKS,    first_char, call,  "0: the block and quarter decisions of the culled classification decode the vertex runs instead of loading whole 16 B words of sign codes (chunk descriptors)") \
   CFX_SWITCH(STEP_SPECULATE,     first_char, call,  "0: steps publish nothing, every size is read back where it is produced") \
   CFX_SWITCH(FUSED_TILES,        integer,    once,  "n: count + offsets + write of a sync-free step as one chained launch up to n tiles (default 512; 0: three launches)") \
   CFX_SWITCH(SCAN_CHAINED_TILES, integer,    once,  "n: scans up to n tiles in one chained launch (default 8192), longer ones in three") \

@@ -228,6 +228,13 @@ class CutData:
         _lib.check(_lib.lib().cfx_cut_domain(self._h, level_set, C.byref(p)))
         return _lib.download(p.value, self.num_local_cells, np.int8)
 
+    def uniform_blocks(self) -> tuple[int, int] | None:
+        """(all inside, all outside): the blocks of 1024 cells that the last classification of level set 0 decided from
+        their vertices' signs alone; None when it went cell by cell.  One read-back: diagnostics, not for a step."""
+        a, b = C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().cfx_cut_uniform_blocks(self._h, C.byref(a), C.byref(b)))
+        return None if a.value < 0 else (int(a.value), int(b.value))
+
     def __del__(self):
         try:
             if self._h:

@@ -289,6 +289,11 @@ int cfx_cut_info(cfx_cut_t cut, int* tdim, int* gdim, int64_t* num_local_cells,
                  int* n_level_sets);
 /* ParentCellClassification::domain(ls, cell) for all cells: device int8 [ncells] */
 int cfx_cut_domain(cfx_cut_t cut, int level_set, const int8_t** domain);
+/* Blocks of 1024 consecutive cells that the last classification of level set 0 decided whole, from the sign codes of
+ * their vertices alone: all inside / all outside.  Both -1 when that classification went cell by cell (facet hosts, a
+ * cell subset, a level set that is not P1 on the geometry, CFX_CLASSIFY_CULL=0).  Counts on the GPU and reads the two
+ * numbers back in one round trip: diagnostics ("path taken"), not for use inside a step.  No reference counterpart. */
+int cfx_cut_uniform_blocks(cfx_cut_t cut, int64_t* n_inside, int64_t* n_outside);
 /* locate_entities(): cut.cpp:877-924.  *entities is owned by `cut` until the
  * next locate call with the same selector or cfx_cut_destroy. */
 int cfx_locate_entities(cfx_cut_t cut, const char* selector,
