@@ -16,13 +16,14 @@
 //   band       with max_distance = B > 0 a value is usable as a source only while it is <= B; the output is min(d, B)
 //   result     phi_v <- s_v d_v
 //
-// U in closed form.  For a sub-face with rows P_s = x_s - x_t, Gram matrix G = P P^T and the values shifted by the first
-// one (delta_s = d_s - d_0: every term of the quadratic then has the size of the cell, nothing cancels against the
-// distance itself), r = d - d_0 is the larger root of (e^T adj e) r^2 - 2 (e^T adj delta) r + delta^T adj delta - det = 0
-// (adj = det G^-1).  It is the minimum over the sub-face's plane, and lies in the sub-face when adj (delta - r e) <= 0
-// componentwise; otherwise a smaller sub-face holds the minimum, so U is the least valid value over all sub-faces (a
-// single vertex is always valid).  A face counts as degenerate relative to its own size (det <= 1e-20 x the product of
-// the diagonal); its sub-faces decide then.
+// U in closed form (cfx_reinit_cell.h has the arithmetic, and the near field's).  For a sub-face of two or three sources,
+// in an orthogonal frame of the sub-face itself: g the gradient of the interpolated d within it, z the foot of the
+// perpendicular from x_t on its plane, h the height of x_t; the minimum over the plane is d(z) + h sqrt(1 - |g|^2), at
+// y = z - h g / sqrt(1 - |g|^2).  It is the sub-face's when y lies in it; otherwise (or with |g| >= 1) a smaller sub-face
+// holds the minimum, so U is the least valid value over all sub-faces (a single vertex is always valid).  Every quantity
+// is conditioned like the sub-face, none like the cell: a flat cell (h small) loses nothing.  A face of three sources
+// counts as degenerate when the sin^2 of its angle at its first source is <= 1e-9 (kDegenerate), two sources when they
+// coincide; the sub-faces decide then.
 //
 // Launches.
 //   reinit_begin   d = inf_value, the mark bits and the record cleared
@@ -46,15 +47,16 @@
 // sweep launched on an empty list returns at once, so the result does not depend on how often the host looks
 // (check_every); with check_every = 0, a device phi and a device info the call makes no host round trip.
 #include "cfx_device.h"
+#include "cfx_reinit_cell.h"
 
 using namespace cfx;
+using namespace cfx::reinit;
 
 namespace
 {
 constexpr int kGroup = 8;        // lanes per target (24 tetrahedra / 6 triangles around a Kuhn vertex)
 constexpr int kTargets = kBlock / kGroup;
 constexpr int kMaxGrid = 4096;   // blocks of the sweep kernels (the list length is on the device: they stride)
-constexpr double kDegenerate = 1e-20;
 
 struct ReinitRecord
 {
@@ -82,157 +84,6 @@ struct ReinitArgs
 };
 
 __device__ __forceinline__ bool usable(const ReinitArgs& A, double v) { return v < A.inf && (A.band <= 0.0 || v <= A.band); }
-
-// ---- distances to the interface piece of a seed cell -------------------------------------------------------------------
-template <int D>
-__host__ __device__ __forceinline__ double seg_dist2(const double* p, const double* a, const double* b)
-{
-  double l2 = 0.0, t = 0.0;
-#pragma unroll
-  for (int k = 0; k < D; ++k)
-  {
-    l2 += (b[k] - a[k]) * (b[k] - a[k]);
-    t += (b[k] - a[k]) * (p[k] - a[k]);
-  }
-  t = l2 > 0.0 ? fmin(fmax(t / l2, 0.0), 1.0) : 0.0;
-  double r2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < D; ++k)
-  {
-    const double w = (p[k] - a[k]) - t * (b[k] - a[k]);
-    r2 += w * w;
-  }
-  return r2;
-}
-
-__host__ __device__ __forceinline__ void cross3(const double* u, const double* v, double* w)
-{
-  w[0] = u[1] * v[2] - u[2] * v[1];
-  w[1] = u[2] * v[0] - u[0] * v[2];
-  w[2] = u[0] * v[1] - u[1] * v[0];
-}
-__host__ __device__ __forceinline__ double dot3(const double* u, const double* v) { return u[0] * v[0] + u[1] * v[1] + u[2] * v[2]; }
-
-// the three edges, and the foot of the perpendicular where it falls inside
-__host__ __device__ __forceinline__ double tri_dist2(const double* p, const double* a, const double* b, const double* c)
-{
-  double r2 = fmin(fmin(seg_dist2<3>(p, a, b), seg_dist2<3>(p, b, c)), seg_dist2<3>(p, c, a));
-  double ab[3], ac[3], bc[3], n[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-  {
-    ab[k] = b[k] - a[k];
-    ac[k] = c[k] - a[k];
-    bc[k] = c[k] - b[k];
-  }
-  cross3(ab, ac, n);
-  const double nn = dot3(n, n);
-  if (nn > kDegenerate * dot3(ab, ab) * dot3(ac, ac))
-  {
-    double w[3], qa[3], qb[3], qc[3], t[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) w[k] = p[k] - a[k];
-    const double s = dot3(n, w);
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-    {
-      const double q = p[k] - n[k] * (s / nn);
-      qa[k] = q - a[k];
-      qb[k] = q - b[k];
-      qc[k] = q - c[k];
-    }
-    cross3(ab, qa, t);
-    const double e0 = dot3(t, n);
-    cross3(bc, qb, t);
-    const double e1 = dot3(t, n);
-    double ca[3] = {-ac[0], -ac[1], -ac[2]};
-    cross3(ca, qc, t);
-    const double e2 = dot3(t, n);
-    if (e0 >= 0.0 && e1 >= 0.0 && e2 >= 0.0) r2 = fmin(r2, s * s / nn);
-  }
-  return r2;
-}
-
-// p = x_i + phi_i / (phi_i - phi_j) (x_j - x_i), i the negative end
-template <int D>
-__host__ __device__ __forceinline__ void crossing(const double (*X)[D], const double* f, int i, int j, double* p)
-{
-  if (!(f[i] < 0.0))
-  {
-    const int s = i;
-    i = j;
-    j = s;
-  }
-  const double t = f[i] / (f[i] - f[j]);
-#pragma unroll
-  for (int k = 0; k < D; ++k) p[k] = X[i][k] + t * (X[j][k] - X[i][k]);
-}
-
-// the distances of the NV vertices of a cell to its interface piece; false: no edge of the cell is crossed
-template <int TDIM>
-__host__ __device__ __forceinline__ bool seed_cell(const double (*X)[TDIM], const double* f, double* dist)
-{
-  constexpr int NV = TDIM + 1;
-  int nneg = 0;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) nneg += f[i] < 0.0 ? 1 : 0;
-  if (nneg == 0 || nneg == NV) return false;
-  if constexpr (TDIM == 2)
-  {
-    // the vertex alone on its side, and the two edges that leave it
-    const bool lone_neg = nneg == 1;
-    int l = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-      if ((f[i] < 0.0) == lone_neg) l = i;
-    double p0[2], p1[2];
-    crossing<2>(X, f, l, (l + 1) % 3, p0);
-    crossing<2>(X, f, l, (l + 2) % 3, p1);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) dist[i] = sqrt(seg_dist2<2>(X[i], p0, p1));
-  }
-  else
-  {
-    double P[4][3];
-    int np = 3;
-    if (nneg == 2)
-    {
-      int neg[2] = {0, 0}, pos[2] = {0, 0}, a = 0, b = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-      {
-        if (f[i] < 0.0) neg[a++] = i;
-        else pos[b++] = i;
-      }
-      // cyclic order ac, ad, bd, bc
-      crossing<3>(X, f, neg[0], pos[0], P[0]);
-      crossing<3>(X, f, neg[0], pos[1], P[1]);
-      crossing<3>(X, f, neg[1], pos[1], P[2]);
-      crossing<3>(X, f, neg[1], pos[0], P[3]);
-      np = 4;
-    }
-    else
-    {
-      const bool lone_neg = nneg == 1;
-      int l = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if ((f[i] < 0.0) == lone_neg) l = i;
-      int q = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i != l) crossing<3>(X, f, l, i, P[q++]);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-    {
-      double r2 = tri_dist2(X[i], P[0], P[1], P[2]);
-      if (np == 4) r2 = fmin(r2, tri_dist2(X[i], P[0], P[2], P[3]));
-      dist[i] = sqrt(r2);
-    }
-  }
-  return true;
-}
 
 __device__ __forceinline__ void lower(double* d, int64_t v, double value)
 {
@@ -411,66 +262,6 @@ __global__ void __launch_bounds__(kBlock) reinit_start_kernel(ReinitArgs A)
   WaveQueue Q{s_queue[threadIdx.x >> 6], 0};
   mark_neighbours<TDIM>(A, src, (int32_t)v, 0, 1, Q, A.list[0], &A.rec->count[0]);
   queue_flush_block(Q, A.list[0], &A.rec->count[0]);
-}
-
-// ---- the update --------------------------------------------------------------------------------------------------------
-// two sources: Gram entries a = |P1|^2, b = P1.P2, c = |P2|^2
-__host__ __device__ __forceinline__ double pair_update(double a, double b, double c, double d1, double d2, double inf)
-{
-  const double det = a * c - b * b;
-  if (!(det > kDegenerate * a * c)) return inf;
-  const double qa = a + c - 2.0 * b, dl = d2 - d1;
-  const double disc = det * (qa - dl * dl);
-  if (!(disc >= 0.0)) return inf;
-  const double r = ((a - b) * dl + sqrt(disc)) / qa;
-  const double mu1 = -c * r - b * (dl - r), mu2 = b * r + a * (dl - r);
-  return (mu1 <= 0.0 && mu2 <= 0.0) ? d1 + r : inf;
-}
-
-__host__ __device__ __forceinline__ double triple_update(const double (*G)[3], const double* dv, double inf)
-{
-  const double a00 = G[1][1] * G[2][2] - G[1][2] * G[1][2], a01 = G[0][2] * G[1][2] - G[0][1] * G[2][2],
-               a02 = G[0][1] * G[1][2] - G[0][2] * G[1][1], a11 = G[0][0] * G[2][2] - G[0][2] * G[0][2],
-               a12 = G[0][1] * G[0][2] - G[0][0] * G[1][2], a22 = G[0][0] * G[1][1] - G[0][1] * G[0][1];
-  const double det = G[0][0] * a00 + G[0][1] * a01 + G[0][2] * a02;
-  if (!(det > kDegenerate * G[0][0] * G[1][1] * G[2][2])) return inf;
-  const double d1 = dv[1] - dv[0], d2 = dv[2] - dv[0];
-  const double e0 = a00 + a01 + a02, e1 = a01 + a11 + a12, e2 = a02 + a12 + a22;
-  const double f0 = a01 * d1 + a02 * d2, f1 = a11 * d1 + a12 * d2, f2 = a12 * d1 + a22 * d2;
-  const double qa = e0 + e1 + e2, qb = f0 + f1 + f2, qc = d1 * f1 + d2 * f2 - det;
-  const double disc = qb * qb - qa * qc;
-  if (!(disc >= 0.0)) return inf;
-  const double r = (qb + sqrt(disc)) / qa;
-  return (f0 - r * e0 <= 0.0 && f1 - r * e1 <= 0.0 && f2 - r * e2 <= 0.0) ? dv[0] + r : inf;
-}
-
-// U(t, K): P[s] = x_s - x_t and dv[s] for the TDIM other vertices of K, ok[s]: usable as a source
-template <int TDIM>
-__host__ __device__ __forceinline__ double cell_update(const double (*P)[TDIM], const double* dv, const bool* ok, double inf)
-{
-  double G[TDIM][TDIM];
-#pragma unroll
-  for (int i = 0; i < TDIM; ++i)
-#pragma unroll
-    for (int j = i; j < TDIM; ++j)
-    {
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < TDIM; ++k) s += P[i][k] * P[j][k];
-      G[i][j] = G[j][i] = s;
-    }
-  double best = inf;
-#pragma unroll
-  for (int i = 0; i < TDIM; ++i)
-    if (ok[i]) best = fmin(best, dv[i] + sqrt(G[i][i]));
-#pragma unroll
-  for (int i = 0; i < TDIM; ++i)
-#pragma unroll
-    for (int j = i + 1; j < TDIM; ++j)
-      if (ok[i] && ok[j]) best = fmin(best, pair_update(G[i][i], G[i][j], G[j][j], dv[i], dv[j], inf));
-  if constexpr (TDIM == 3)
-    if (ok[0] && ok[1] && ok[2]) best = fmin(best, triple_update(G, dv, inf));
-  return best;
 }
 
 template <int TDIM>

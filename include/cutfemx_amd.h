@@ -766,10 +766,14 @@ int cfx_minres_solve(int64_t nrows, const int64_t* indptr, const int32_t* indice
  *   result      phi_v <- s_v d_v; an exact zero stays +0.0; a vertex never reached gets s_v min(inf_value, max_distance)
  * The iteration is monotone: its limit does not depend on the order of the updates.  The engine runs Jacobi-type
  * sweeps over the list of vertices next to a change.  Two calls on the same inputs give the same bits.
- * Deviations from the reference, on purpose: the 3-point update is the closed form (the larger root of the quadratic of
- * the face's Gram matrix, valid while its multipliers are <= 0) instead of a 20-step Newton iteration
- * (eikonal_update.h:157-255); a face is degenerate relative to its own size (eikonal_update.h:144 tests |cross|^2 <
- * 1e-14); an improvement is accepted when it is strict (new < old), without the reference's absolute 1e-13 slack.
+ * Deviations from the reference, on purpose: the 3-point update is a closed form (in an orthogonal frame of the face: g
+ * the gradient of d within the face, h the height of x_t over its plane, z the foot of the perpendicular; U = d(z) +
+ * h sqrt(1 - |g|^2) at y = z - h g / sqrt(1 - |g|^2), valid while y lies in the face) instead of a 20-step Newton
+ * iteration (eikonal_update.h:157-255).  U is within 1e-10 x the cell's size of the true minimum whatever the shape of
+ * the cell (a flat cell loses nothing), and never below it by more.  A face of three sources is degenerate relative to its
+ * own size, when the sin^2 of its angle at its first source (in the cell's vertex order) is <= 1e-9 (eikonal_update.h:144
+ * tests |cross|^2 < 1e-14); two sources are when they coincide; a degenerate face is decided by its sub-faces.  An
+ * improvement is accepted when it is strict (new < old), without the reference's absolute 1e-13 slack.
  * max_distance = B > 0 (the one extension): a value is used as a source, and activates its neighbours, only while it
  * is <= B, and the output is clamped to B -- the result is where(d <= B, d, B) of the unbanded one after about B / h
  * sweeps instead of (largest distance) / h.

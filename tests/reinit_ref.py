@@ -1,7 +1,9 @@
 """numpy model of the reinitialisation contract (include/cutfemx_amd.h, cfx_reinitialize), written from the contract:
-sign, near field from the crossing points of the seed cells, the update U(t, K) as the least valid Gram-form value over
-the finite sub-faces, Jacobi sweeps to the exact fixed point.  Shared by tests/test_reinit_reference.py (which pins it to
-mathematics) and the GPU tests (which compare the engine with it on the same arrays).  Every case's model runs once."""
+sign, near field from the crossing points of the seed cells, the update U(t, K) as the least valid value over the finite
+sub-faces, each in an orthonormal frame of its own, Jacobi sweeps to the exact fixed point.  Shared by
+tests/test_reinit_reference.py (which pins it to mathematics) and the GPU tests (which compare the engine with it on the
+same arrays).  Every case's model runs once.  The cell-local parts (nearfield, update) are themselves checked against
+the independent references of tests/reinit_exact.py in tests/test_reinit_cell_reference.py."""
 from __future__ import annotations
 
 from itertools import combinations
@@ -10,7 +12,8 @@ import numpy as np
 
 INF = 1e30
 CONVERGED, MAX_ITER, NO_INTERFACE = 1, 2, 3
-DEGENERATE = 1e-20
+DEGENERATE = 1e-9     # the update: kDegenerate of cutfemx_amd/csrc/cfx_reinit_cell.h
+FLAT_PIECE = 1e-20    # the near field: kFlatPiece
 
 
 # ---- near field ---------------------------------------------------------------------------------------------------------
@@ -28,7 +31,7 @@ def _tri_dist2(p, a, b, c):
     ab, ac, bc = b - a, c - a, c - b
     n = np.cross(ab, ac)
     nn = np.einsum("ij,ij->i", n, n)
-    good = nn > DEGENERATE * np.einsum("ij,ij->i", ab, ab) * np.einsum("ij,ij->i", ac, ac)
+    good = nn > FLAT_PIECE * np.einsum("ij,ij->i", ab, ab) * np.einsum("ij,ij->i", ac, ac)
     nn1 = np.where(good, nn, 1.0)
     s = np.einsum("ij,ij->i", n, p - a)
     q = p - n * (s / nn1)[:, None]
@@ -87,10 +90,52 @@ def nearfield(x, conn, phi, inf=INF):
 
 
 # ---- the update ---------------------------------------------------------------------------------------------------------
+def _subface_value(Ps, ds, inf):
+    """The minimum of d + |x_t - y| over the PLANE of a sub-face of two or three sources, where it lies in the sub-face,
+    else inf.  In an orthonormal frame (u_1, ...) of the sub-face: g the gradient of d within it, z the foot of the
+    perpendicular from the target, h its height; U = d(z) + h sqrt(1 - |g|^2) at y = z - h g / sqrt(1 - |g|^2)."""
+    m, size, _ = Ps.shape
+    val = np.full(m, inf)
+    E = Ps[:, 1:, :] - Ps[:, :1, :]                           # edges from the first source
+    delta = ds[:, 1:] - ds[:, :1]
+    l1 = np.linalg.norm(E[:, 0], axis=1)
+    good = l1 > 0.0
+    if size == 3:
+        e2e2 = np.einsum("mk,mk->m", E[:, 1], E[:, 1])
+        with np.errstate(all="ignore"):
+            u1 = E[:, 0] / l1[:, None]
+            w = E[:, 1] - np.einsum("mk,mk->m", E[:, 1], u1)[:, None] * u1
+            ww = np.einsum("mk,mk->m", w, w)
+        good &= ww > DEGENERATE * e2e2                        # sin^2 of the angle at the first source
+    rows = np.nonzero(good)[0]
+    if rows.size == 0:
+        return val
+    E, delta, P0, d0 = E[rows], delta[rows], Ps[rows, 0], ds[rows, 0]
+    # frame and the edges' coordinates in it: E = C U, C lower triangular
+    U = np.zeros((rows.size, size - 1, E.shape[2]))
+    U[:, 0] = E[:, 0] / np.linalg.norm(E[:, 0], axis=1)[:, None]
+    if size == 3:
+        w = E[:, 1] - np.einsum("mk,mk->m", E[:, 1], U[:, 0])[:, None] * U[:, 0]
+        U[:, 1] = w / np.linalg.norm(w, axis=1)[:, None]
+    Cm = np.einsum("mik,mjk->mij", E, U)
+    g = np.linalg.solve(Cm, delta[:, :, None])[:, :, 0]       # gradient in the frame
+    gg = 1.0 - np.einsum("mi,mi->m", g, g)
+    real = gg > 0.0
+    root = np.sqrt(np.where(real, gg, 1.0))
+    pt = np.einsum("mik,mk->mi", U, P0)                       # the first source in the frame (the target is the origin)
+    z = P0 - np.einsum("mi,mik->mk", pt, U)                   # foot of the perpendicular
+    h = np.linalg.norm(z, axis=1)
+    y = -pt - (h / root)[:, None] * g                         # y - P0 in the frame
+    lam = np.linalg.solve(np.swapaxes(Cm, 1, 2), y[:, :, None])[:, :, 0]
+    valid = real & np.all(lam >= 0.0, axis=1) & (lam.sum(axis=1) <= 1.0)
+    val[rows] = np.where(valid, d0 - np.einsum("mi,mi->m", g, pt) + h * root, inf)
+    return val
+
+
 def update(P, dv, ok, inf=INF):
     """U for m (target, cell) pairs: P[m, k, dim] = x_s - x_t and dv[m, k] of the k other vertices, ok[m, k] usable.
-    The least valid value over every non-empty sub-face: with G = P P^T and delta = d - d_0, r = d - d_0 is the larger
-    root of (e G^-1 e) r^2 - 2 (e G^-1 delta) r + delta G^-1 delta - 1 = 0, valid when G^-1 (delta - r e) <= 0."""
+    The least valid value over every non-empty sub-face (a single source is always valid; a face of three sources whose
+    sin^2 at its first source is not above DEGENERATE is left to its sub-faces)."""
     m, k, _ = P.shape
     best = np.full(m, inf)
     for size in range(1, k + 1):
@@ -100,26 +145,10 @@ def update(P, dv, ok, inf=INF):
             if rows.size == 0:
                 continue
             Ps, ds = P[rows][:, S, :], dv[rows][:, S]
-            G = np.einsum("mik,mjk->mij", Ps, Ps)
             if size == 1:
-                val = ds[:, 0] + np.sqrt(G[:, 0, 0])
-                best[rows] = np.minimum(best[rows], val)
-                continue
-            good = np.linalg.det(G) > DEGENERATE * np.prod(np.einsum("mii->mi", G), axis=1)
-            rows, G, ds = rows[good], G[good], ds[good]
-            if rows.size == 0:
-                continue
-            delta = ds - ds[:, :1]
-            e = np.ones_like(delta)
-            Ge = np.linalg.solve(G, e[:, :, None])[:, :, 0]
-            Gd = np.linalg.solve(G, delta[:, :, None])[:, :, 0]
-            A, B, Cq = Ge.sum(axis=1), Gd.sum(axis=1), np.einsum("mi,mi->m", delta, Gd) - 1.0
-            disc = B * B - A * Cq
-            real = disc >= 0.0
-            r = (B + np.sqrt(np.where(real, disc, 0.0))) / A
-            mu = Gd - r[:, None] * Ge
-            valid = real & np.all(mu <= 0.0, axis=1)
-            val = np.where(valid, ds[:, 0] + r, inf)
+                val = ds[:, 0] + np.linalg.norm(Ps[:, 0], axis=1)
+            else:
+                val = _subface_value(Ps, ds, inf)
             best[rows] = np.minimum(best[rows], val)
     return best
 
