@@ -149,6 +149,9 @@ struct RowArgs
   const double* cut_tensors;
   const unsigned long long* cut_bits;
   const int32_t* cut_rank;
+  // degree 1, scalar: the rule_tensors of the cell slots hold ONE record per cut cell, at the cell's first rule in the lowest
+  // slot in which it has one (cut_combine_p1_kernel); the records at the other rules are not written
+  int cut_combined;
 };
 
 // index of cell c in the sorted entity list described by (bits, rank)
@@ -1486,6 +1489,7 @@ __global__ void __launch_bounds__(kWave, DEG > 1 ? (CUTS ? (CUTT ? (STD ? 3 : 4)
         {
 #pragma unroll
           for (int j = 0; j < ND; ++j) csl[j] = find_slot(cd[k][j]);
+          bool cut_done = false; // cut_combined: the cell's one record has been read
           for (int i = 0; i < A.n_cell; ++i)
           {
             const RowIntegral& I = A.cell[i];
@@ -1526,7 +1530,38 @@ __global__ void __launch_bounds__(kWave, DEG > 1 ? (CUTS ? (CUTT ? (STD ? 3 : 4)
             }
             if (CUTS && !CUTT && (mark & (16u << i)))
             {
-              if (DEG == 2 && I.rule_moments)
+              if (DEG == 1 && A.cut_combined)
+              {
+                if constexpr (DEG == 1)
+                {
+                  // one record per cut cell, at its host rule: the first marked slot (ascending) whose map holds the cell
+                  if (!cut_done && I.rule_tensors != nullptr)
+                  {
+                    const int64_t e = first_rule(I.rule_keys, I.rule_first, I.rule_mask, (int32_t)c);
+                    if (e < dev_len(I.nr) && I.parent_map[e] == c)
+                    {
+                      cut_done = true;
+                      const double* T = I.rule_tensors + (e * ND + lr) * ND;
+                      if constexpr (ND % 2 == 0)
+                      {
+                        const double2* T2 = reinterpret_cast<const double2*>(T);
+#pragma unroll
+                        for (int j = 0; j < ND / 2; ++j)
+                        {
+                          const double2 v = T2[j];
+                          acc[2 * j] += v.x; acc[2 * j + 1] += v.y;
+                        }
+                      }
+                      else
+                      {
+#pragma unroll
+                        for (int j = 0; j < ND; ++j) acc[j] += T[j];
+                      }
+                    }
+                  }
+                }
+              }
+              else if (DEG == 2 && I.rule_moments)
               {
                 if constexpr (DEG == 2)
                 {
@@ -4043,6 +4078,218 @@ __global__ void __launch_bounds__(kBlock, CFX_CUTT_WAVES) cut_tensors_p2_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Degree 1, scalar, bilinear forms: the rule integrals of a cut cell summed in stage 1 (CFX_P1_CUT_COMBINE=0: one
+// tensor per rule and integral).  The sum over every rule of the cell in every rule-carrying cell slot of the form is
+// stored in the staging buffer that exists anyway, at the cell's HOST RULE: its first rule in the lowest slot in which
+// it has one (read from that slot's hash map, not from the mark bit).  The gather then takes one probe and one record
+// per (row, cut cell) item.  Records at the other rules are not written and never read.  No list, no count and no
+// read-back: the launch covers the rules of all slots (thread ranges like cfx::RuleJobs, sized by the capacities)
+// and a lane group leaves unless it sits at a host rule.  Order of the sum: slots ascending, rules ascending, the
+// points of a rule dealt round-robin to the lanes, then one fixed shuffle tree -- bitwise reproducible.
+// ---------------------------------------------------------------------------
+struct CombineSlot
+{
+  int kernel, point_stride;
+  double params[3];
+  const int32_t* offsets;
+  const int32_t* parent_map;
+  DevN n;     // rules of the slot (length in HBM inside a sync-free step)
+  DevN bound; // rule_bound(): where the walk over a parent's rules ends at the latest
+  const double* points;
+  const double* weights;
+  const double* point_data;
+  const int32_t* keys;
+  const int32_t* first;
+  unsigned mask;
+  double* out; // the slot's staging, [n.cap][ND * ND]; null: the slot carries no rules
+};
+struct CombineArgs
+{
+  const double* x;
+  const int32_t* conn;
+  int n_slots;
+  int64_t start[5]; // slot k covers the threads [start[k], start[k + 1]), whole blocks
+  CombineSlot slot[4];
+};
+#ifndef CFX_COMBINE_LANES
+#define CFX_COMBINE_LANES 2 // lanes per host rule (512^3: 1 -> 1.19 ms, 2 -> 0.77, 4 -> 0.88, 8 -> 1.62)
+#endif
+constexpr int kCombineLanes = CFX_COMBINE_LANES;
+constexpr int64_t kNoRule = 0x7fffffff; // first_rule(): the cell has no rule in the map
+
+// The rule this lane group sits at, if it is a host rule: slot k, rule e, parent c; rf[t]: the cell's first rule in
+// slot t (rf[k] = e, kNoRule: none) and vid: its vertices.  The maps of the other slots are probed whatever the cell's
+// mark says (a rule sets the mark bit, so the marked slots are among the probed ones): the probes depend on the parent
+// alone and are in flight together with the connectivity row, one level of dependent loads instead of three
+template <int ND>
+__device__ __forceinline__ bool combine_host_rule(const CombineArgs& A, int& k, int64_t& e, int& sub, int32_t& c,
+                                                  int64_t (&rf)[4], int32_t (&vid)[ND])
+{
+  const int64_t b0 = (int64_t)blockIdx.x * kBlock; // (the slot is the same for the whole block)
+  k = 0;
+  while (k + 1 < A.n_slots && b0 >= A.start[k + 1]) ++k;
+  const CombineSlot& S = A.slot[k];
+  const int64_t tid = b0 - A.start[k] + threadIdx.x;
+  e = tid / kCombineLanes;
+  sub = (int)(tid - e * kCombineLanes);
+  if (S.out == nullptr || e >= dev_n(S.n)) return false;
+  c = S.parent_map[e];
+  if (e > 0 && S.parent_map[e - 1] == c) return false; // not the first rule of its parent
+  if constexpr (ND == 4)
+  {
+    const int4 v = *reinterpret_cast<const int4*>(A.conn + (int64_t)c * 4);
+    vid[0] = v.x; vid[1] = v.y; vid[2] = v.z; vid[3] = v.w;
+  }
+  else
+  {
+#pragma unroll
+    for (int j = 0; j < ND; ++j) vid[j] = A.conn[(int64_t)c * ND + j];
+  }
+  bool lower = false; // a lower slot hosts the cell
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+  {
+    rf[t] = kNoRule;
+    if (t == k) rf[t] = e;
+    else if (t < A.n_slots && A.slot[t].out != nullptr)
+    {
+      rf[t] = first_rule(A.slot[t].keys, A.slot[t].first, A.slot[t].mask, c);
+      lower = lower || (t < k && rf[t] != kNoRule);
+    }
+  }
+  return !lower;
+}
+
+#ifndef CFX_COMBINE_WAVES
+#define CFX_COMBINE_WAVES 4 // waves per SIMD (cut_tensors_p1_kernel: 126 registers under the same bound)
+#endif
+template <int TDIM>
+__global__ void __launch_bounds__(kBlock, CFX_COMBINE_WAVES) cut_combine_p1_kernel(CombineArgs A)
+{
+  constexpr int ND = TDIM + 1, L = kCombineLanes;
+  int k, sub;
+  int64_t e, rf[4];
+  int32_t c, vid[ND];
+  if (!combine_host_rule<ND>(A, k, e, sub, c, rf, vid)) return;
+  Geo<TDIM> g;
+#pragma unroll
+  for (int i = 0; i < ND; ++i) load_vertex<TDIM>(A.x, vid[i], g.x[i]);
+  jacobian<TDIM>(g);
+  const double h = cell_diameter<TDIM>(g);
+  // physical gradients of the barycentric basis: G_j = K^T dN_j, dN_0 = -1, dN_t = e_t (cut_tensors_p1_kernel)
+  double G[ND][TDIM];
+#pragma unroll
+  for (int d = 0; d < TDIM; ++d)
+  {
+    double s = 0.0;
+#pragma unroll
+    for (int t = 0; t < TDIM; ++t) { G[t + 1][d] = g.K[t][d]; s += g.K[t][d]; }
+    G[0][d] = -s;
+  }
+  // Nitsche / mass sums (symmetric: the upper triangle, 10 instead of 16 accumulators in 3-D -- the full tensor next to
+  // the gradients spilled under the 4-waves bound), and the weights of the stiffness rules
+  constexpr int NP = ND * (ND + 1) / 2;
+  double U[NP], wsum = 0.0;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) U[p] = 0.0;
+  for (int t = k; t < A.n_slots; ++t)
+  {
+    const CombineSlot& R = A.slot[t];
+    const int64_t r0 = t == 0 ? rf[0] : (t == 1 ? rf[1] : (t == 2 ? rf[2] : rf[3]));
+    if (r0 == kNoRule) continue;
+    const int64_t end = dev_len(R.bound);
+    const double gam = R.kernel == CFX_K_NITSCHE ? R.params[0] / h : 0.0;
+    for (int64_t r = r0; r < end && R.parent_map[r] == c; ++r)
+    {
+      const int32_t q0 = R.offsets[r], q1 = R.offsets[r + 1];
+      if (R.kernel == CFX_K_STIFFNESS)
+      {
+        for (int32_t q = q0 + sub; q < q1; q += L) wsum += R.weights[q];
+        continue;
+      }
+      for (int32_t q = q0 + sub; q < q1; q += L)
+      {
+        const double w = R.weights[q];
+        double N[ND], l0 = 1.0;
+#pragma unroll
+        for (int v = 0; v < TDIM; ++v) { N[v + 1] = R.points[(int64_t)q * TDIM + v]; l0 -= N[v + 1]; }
+        N[0] = l0;
+        if (R.kernel == CFX_K_MASS)
+        {
+          int p = 0;
+#pragma unroll
+          for (int i = 0; i < ND; ++i)
+#pragma unroll
+            for (int j = i; j < ND; ++j) U[p++] += w * N[i] * N[j];
+        }
+        else // Nitsche: -dn(u) v - dn(v) u + gamma/h u v with the per-point normal
+        {
+          const double* nrm = R.point_data + (int64_t)q * R.point_stride;
+          double dn[ND];
+#pragma unroll
+          for (int j = 0; j < ND; ++j)
+          {
+            double s = 0.0;
+#pragma unroll
+            for (int d = 0; d < TDIM; ++d) s += G[j][d] * nrm[d];
+            dn[j] = s;
+          }
+          int p = 0;
+#pragma unroll
+          for (int i = 0; i < ND; ++i)
+#pragma unroll
+            for (int j = i; j < ND; ++j) U[p++] += w * (-dn[j] * N[i] - dn[i] * N[j] + gam * N[j] * N[i]);
+        }
+      }
+    }
+  }
+  // (the lanes of a group took the same path to this point: every lane the tree reads from is here)
+#pragma unroll
+  for (int o = L / 2; o > 0; o >>= 1) wsum += __shfl_xor(wsum, o, L);
+  {
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+#pragma unroll
+      for (int j = i; j < ND; ++j)
+      {
+#pragma unroll
+        for (int o = L / 2; o > 0; o >>= 1) U[p] += __shfl_xor(U[p], o, L);
+        double s = 0.0;
+#pragma unroll
+        for (int d = 0; d < TDIM; ++d) s += G[i][d] * G[j][d];
+        U[p] += wsum * s;
+        ++p;
+      }
+  }
+  // lane i of the group stores row i
+  double* out = A.slot[k].out + e * (ND * ND);
+#pragma unroll
+  for (int i = 0; i < ND; ++i)
+  {
+    if (i % L != sub) continue;
+    double row[ND];
+#pragma unroll
+    for (int j = 0; j < ND; ++j)
+    {
+      const int a = i < j ? i : j, b = i < j ? j : i;
+      row[j] = U[a * ND - a * (a - 1) / 2 + (b - a)];
+    }
+    if constexpr (ND % 2 == 0)
+    {
+      double2* o2 = reinterpret_cast<double2*>(out + i * ND);
+#pragma unroll
+      for (int j = 0; j < ND / 2; ++j) o2[j] = make_double2(row[2 * j], row[2 * j + 1]);
+    }
+    else
+    {
+#pragma unroll
+      for (int j = 0; j < ND; ++j) out[i * ND + j] = row[j];
+    }
+  }
+}
+
 struct Stage1
 {
   std::vector<DevArray<double>> buffers;
@@ -4281,12 +4528,36 @@ inline bool p2_cut_tensors_ok(const cfx_form_s* a)
   return any;
 }
 
+// the rule integrals of a degree-1 scalar bilinear form that stage 1 can sum into one tensor per cut cell
+// (cut_combine_p1_kernel): at least two cell slots carry rules (a single one gains nothing), every one of them an
+// integrand that kernel knows, without a coefficient.  (Linear forms keep one vector per rule: the same sum in their
+// stage 1 cost what the gather saved -- DESIGN.md section 3 round 13.)
+inline bool p1_cut_combine_ok(const cfx_form_s* a, const cfx_row_plan& plan)
+{
+  if (!env_on<Sw::P1_CUT_COMBINE>() || !env_on<Sw::CUT_TENSORS_P1>()) return false;
+  if (a->V->degree != 1 || a->V->bs != 1 || a->rank != 2) return false;
+  int n = 0;
+  for (int s = 0; s < plan.n_cell_slots; ++s)
+  {
+    const cfx_integral_dev& I = a->integrals[plan.cell_slot_integral[s]];
+    if (!I.rules || I.rules->nr.cap() == 0) continue;
+    if (I.coefficient.n > 0 || user_integrand_known(I.kernel)) return false;
+    if (!(I.kernel == CFX_K_STIFFNESS || I.kernel == CFX_K_MASS || I.kernel == CFX_K_NITSCHE)) return false;
+    if (I.kernel == CFX_K_NITSCHE && I.point_data.n == 0) return false; // (no normals)
+    ++n;
+  }
+  return n >= 2;
+}
+
 template <int TDIM, int DEG, int BS = 1>
 RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
 {
   constexpr int ND = Elem<TDIM, DEG>::ND * BS; // local tensor dimension (scalar dofs x block size)
   cfx_row_plan& plan = row_plan(a);
   cfx_space_s* V = a->V;
+  // degree 1, scalar, bilinear: one staged tensor per cut cell
+  bool combine_p1 = false;
+  if constexpr (DEG == 1 && BS == 1) combine_p1 = p1_cut_combine_ok(a, plan);
   RowArgs A{};
   A.x = V->mesh->x.p; A.conn = V->mesh->conn.p; A.dofmap = V->dofmap.p;
   A.iso_geometry = (DEG == 1 && V->dofmap.p == V->mesh->conn.p) ? 1 : 0;
@@ -4360,9 +4631,35 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
       st.buffers.emplace_back(n_rules * (moments ? 16 : tsize));
       R.rule_tensors = st.buffers.back().p;
       R.rule_moments = moments ? 1 : 0;
-      if (moments) dump_cut_moments(a, ii, st.buffers.back().p);
+      if (combine_p1) {} // (one launch for all slots behind this loop)
+      else if (moments) dump_cut_moments(a, ii, st.buffers.back().p);
       else if (a->rank == 2) dump_integral(a, ii, 2, st.buffers.back().p);
       else if constexpr (BS == 1) vec_tensors<TDIM, DEG>(a, I, true, st.buffers.back().p);
+    }
+  }
+  if constexpr (DEG == 1 && BS == 1)
+  {
+    if (combine_p1)
+    {
+      CombineArgs C{};
+      C.x = A.x; C.conn = A.conn; C.n_slots = plan.n_cell_slots;
+      for (int s = 0; s < plan.n_cell_slots; ++s)
+      {
+        const cfx_integral_dev& I = a->integrals[plan.cell_slot_integral[s]];
+        CombineSlot& S = C.slot[s];
+        C.start[s + 1] = C.start[s];
+        if (!A.cell[s].rule_tensors) continue;
+        const cfx_rules_s* R = I.rules;
+        S.kernel = I.kernel; S.point_stride = I.point_stride;
+        for (int k = 0; k < 3; ++k) S.params[k] = I.params[k];
+        S.offsets = R->offsets.p; S.parent_map = R->parent_map.p; S.n = R->nr.devn(); S.bound = rule_bound(R);
+        S.points = R->points.p; S.weights = R->weights.p; S.point_data = I.point_data.n > 0 ? I.point_data.p : nullptr;
+        S.keys = plan.rule_keys[s].p; S.first = plan.rule_first[s].p; S.mask = plan.rule_mask[s];
+        S.out = const_cast<double*>(A.cell[s].rule_tensors);
+        C.start[s + 1] += (S.n.cap * kCombineLanes + kBlock - 1) / kBlock * kBlock;
+      }
+      launch("cut_tensors_p1", cut_combine_p1_kernel<TDIM>, grid_for(C.start[plan.n_cell_slots]), dim3(kBlock), 0, C);
+      A.cut_combined = 1;
     }
   }
   if constexpr (DEG == 2 && BS == 1)

@@ -44,6 +44,7 @@
   CFX_SWITCH(PLAIN_STAGE,        first_char, call,  "0: plain rows without LDS staging, the form that meshes with stencils longer than 32 take by themselves") \
   CFX_SWITCH(MFMA,               first_char, call,  "0: generic rows instead of the MFMA kernel for staged elasticity tensors") \
   CFX_SWITCH(CUT_TENSORS_P1,     first_char, call,  "0: the generic tensors of cut P1 cells") \
+  CFX_SWITCH(P1_CUT_COMBINE,     first_char, call,  "0: one staged tensor per rule and integral of a degree-1 bilinear form instead of one per cut cell") \
   CFX_SWITCH(RECT_GATHER,        first_char, call,  "0: rectangular blocks by the entity-parallel atomic kernel") \
   CFX_SWITCH(BULK_ROWS,          first_char, call,  "0: row plans take their marks from the entity lists, not from the classification") \
   CFX_SWITCH(PATTERN_REUSE,      first_char, call,  "0: never copy rows from the space's previous pattern") \
