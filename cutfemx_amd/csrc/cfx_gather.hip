@@ -188,6 +188,188 @@ __device__ __forceinline__ int64_t lower_bound_i32(const int32_t* __restrict__ a
   return lo;
 }
 
+// ---------------------------------------------------------------------------
+// Building blocks of the stage-2 row kernels: a group of G lanes of a one-wavefront block owns one matrix row, whose
+// CSR slots are accumulated in LDS (`s_col_row` / `s_val_row`: the group's own rows of the kernel's LDS arrays).
+// ---------------------------------------------------------------------------
+// the group's row: lane split, row id and CSR range.  A row longer than the kernel's capacity is reported (error
+// word 2) and skipped (len = 0)
+struct RowHead
+{
+  int grp, gl;
+  int64_t ri;
+  bool live;
+  int64_t r, rb;
+  int len;
+};
+
+template <int G, int CAP>
+__device__ __forceinline__ RowHead row_head(int64_t n_rows, const int32_t* rows, const int64_t* indptr, int* error)
+{
+  RowHead h;
+  const int lane = threadIdx.x;
+  h.grp = lane / G; h.gl = lane % G;
+  h.ri = CFX_ROW_BLOCK * (kWave / G) + h.grp;
+  h.live = h.ri < n_rows;
+  h.r = h.live ? rows[h.ri] : 0;
+  h.rb = h.live ? indptr[h.r] : 0;
+  h.len = h.live ? (int)(indptr[h.r + 1] - h.rb) : 0;
+  if (h.len > CAP) { *error = 2; h.len = 0; }
+  return h;
+}
+
+// Row prologue: this lane's slice of the row's columns, requested in one batch, then stored with zeroed accumulators
+template <int G, int KMAX>
+__device__ __forceinline__ void stage_row_columns(const int32_t* indices, int64_t rb, int len, int gl, int32_t* s_col_row,
+                                                  double* s_val_row)
+{
+  int32_t mycol[KMAX];
+#pragma unroll
+  for (int q = 0; q < KMAX; ++q)
+  {
+    const int k = gl + q * G;
+    mycol[q] = k < len ? indices[rb + k] : -1;
+  }
+#pragma unroll
+  for (int q = 0; q < KMAX; ++q)
+  {
+    const int k = gl + q * G;
+    if (k < len)
+    {
+      s_col_row[k] = mycol[q];
+      s_val_row[k] = 0.0;
+    }
+  }
+}
+
+// The row's columns as an open-addressing hash map column -> CSR slot in LDS (HS keys per row, at least twice the
+// row's capacity: load factor <= 1/2; an empty key is -1)
+template <int HS>
+struct RowHash
+{
+  static_assert((HS & (HS - 1)) == 0, "power of two");
+  static_assert(HS == 128 || HS == 256 || HS == 512 || HS == 1024, "hash shift");
+  static constexpr int kShift = HS == 128 ? 25 : (HS == 256 ? 24 : (HS == 512 ? 23 : 22)); // multiplicative hash: the top log2(HS) bits
+  static __device__ __forceinline__ void insert(int32_t* s_key_row, uint16_t* s_slot_row, int32_t col, int k)
+  {
+    unsigned h = ((uint32_t)col * 2654435761u) >> kShift;
+    while (atomicCAS(&s_key_row[h], -1, col) != -1) h = (h + 1) & (HS - 1); // (columns of a row are distinct)
+    s_slot_row[h] = (uint16_t)k;
+  }
+  // CSR slot of column `col` (-1 and error word 1 if absent)
+  static __device__ __forceinline__ int lookup(const int32_t* s_key_row, const uint16_t* s_slot_row, int32_t col, int* error)
+  {
+    // the first two positions without a branch (load factor <= 1/2: ~9 of 10 lookups end there), both keys in flight
+    // together; the probe loop only behind them (26 loops with data-dependent trip counts per pass were a good part
+    // of the kernel's scalar instructions: as many as vector ones)
+    const unsigned h0 = ((uint32_t)col * 2654435761u) >> kShift, h1 = (h0 + 1) & (HS - 1);
+    const int32_t k0 = s_key_row[h0], k1 = s_key_row[h1];
+    const int v0 = s_slot_row[h0], v1 = s_slot_row[h1]; // (requested with the keys: no dependent LDS read on a hit)
+    if (k0 == col) return v0;
+    if (k1 == col) return v1;
+    if (k0 != -1 && k1 != -1)
+    {
+      unsigned h = (h1 + 1) & (HS - 1);
+      for (int probe = 2; probe < HS; ++probe)
+      {
+        const int32_t key = s_key_row[h];
+        if (key == col) return (int)s_slot_row[h];
+        if (key == -1) break;
+        h = (h + 1) & (HS - 1);
+      }
+    }
+    *error = 1;
+    return -1;
+  }
+};
+
+// CSR slot of column `col` in the row's sorted column list (-1 and error word 1 if absent)
+__device__ __forceinline__ int sorted_slot(const int32_t* s_col_row, int len, int32_t col, int* error)
+{
+  int lo = 0, hi = len;
+  while (lo < hi)
+  {
+    const int mid = (lo + hi) >> 1;
+    if (s_col_row[mid] < col) lo = mid + 1; else hi = mid;
+  }
+  if (lo < len && s_col_row[lo] == col) return lo;
+  *error = 1;
+  return -1;
+}
+
+// add this lane's item -- NC columns, `slots[j]` the CSR slot of column j or -1 -- to its row.  ORDERED keeps item
+// order: one lane of each group at a time, and the barrier (block = one wavefront) orders the LDS read-modify-writes of
+// successive turns; every group of the block must make the call
+template <bool ORDERED, int G, int NC>
+__device__ __forceinline__ void row_add(double* s_val_row, int gl, const int* slots, const double* values)
+{
+  if constexpr (ORDERED)
+  {
+    for (int turn = 0; turn < G; ++turn)
+    {
+      if (gl == turn)
+      {
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+          if (slots[j] >= 0) s_val_row[slots[j]] += values[j];
+      }
+      __syncthreads();
+    }
+  }
+  else
+  {
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+      if (slots[j] >= 0) atomicAdd(&s_val_row[slots[j]], values[j]);
+  }
+}
+
+// dof row of a cell: one 16 B load where the row has four entries
+template <int ND>
+__device__ __forceinline__ void load_dof_row(const int32_t* dofmap, int64_t cell, int32_t* out)
+{
+  if constexpr (ND == 4)
+  {
+    const int4 v = *reinterpret_cast<const int4*>(dofmap + cell * 4);
+    out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
+  }
+  else
+  {
+#pragma unroll
+    for (int j = 0; j < ND; ++j) out[j] = dofmap[cell * ND + j];
+  }
+}
+
+// Row epilogue: `store` (the first and only writer on a matrix that holds nothing yet: set_value(0) fused) stores the
+// reduced row; else values[row] += reduced row, loads batched
+template <int G, int KMAX>
+__device__ __forceinline__ void row_writeback(double* values, int64_t rb, int len, int gl, const double* s_val_row, bool store)
+{
+  if (store)
+  {
+#pragma unroll
+    for (int q = 0; q < KMAX; ++q)
+    {
+      const int k = gl + q * G;
+      if (k < len) values[rb + k] = s_val_row[k];
+    }
+    return;
+  }
+  double myval[KMAX];
+#pragma unroll
+  for (int q = 0; q < KMAX; ++q)
+  {
+    const int k = gl + q * G;
+    myval[q] = k < len ? values[rb + k] : 0.0;
+  }
+#pragma unroll
+  for (int q = 0; q < KMAX; ++q)
+  {
+    const int k = gl + q * G;
+    if (k < len) values[rb + k] = myval[q] + s_val_row[k];
+  }
+}
+
 // 24 B vertex record (stride 3 doubles, 8 B aligned): one 16 B + one 8 B load
 typedef double cfx_d2u __attribute__((ext_vector_type(2), aligned(8)));
 
@@ -1350,23 +1532,7 @@ __global__ void __launch_bounds__(kWave, DEG > 1 ? (CUTS ? (CUTT ? (STD ? 3 : 4)
   if (len > CAP) { *A.error = 2; len = 0; }
   // Row prologue: this lane's slice of the row's columns, requested in one batch
   constexpr int KMAX = CAP / G;
-  int32_t mycol[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    mycol[q] = k < len ? A.indices[rb + k] : -1;
-  }
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    if (k < len)
-    {
-      s_col[grp][k] = mycol[q];
-      s_val[grp][k] = 0.0;
-    }
-  }
+  stage_row_columns<G, KMAX>(A.indices, rb, len, gl, s_col[grp], s_val[grp]);
   __syncthreads();
   const bool cells = live && A.cellmark != nullptr;
   const int64_t cb = cells ? A.d2c_off[r] : 0;
@@ -1381,20 +1547,7 @@ __global__ void __launch_bounds__(kWave, DEG > 1 ? (CUTS ? (CUTT ? (STD ? 3 : 4)
   double dsum = 0.0;
   const bool diag_bc = row_bc || (live && A.bc1 != nullptr && A.bc1[r] != 0);
 
-  // add one item (ncols columns) of every group to its row; ORDERED keeps item order
-  // CSR slot of column `col` of this row (-1 and the error flag if absent)
-  auto find_slot = [&](int32_t col) -> int
-  {
-    int lo = 0, hi = len;
-    while (lo < hi)
-    {
-      const int mid = (lo + hi) >> 1;
-      if (s_col[grp][mid] < col) lo = mid + 1; else hi = mid;
-    }
-    if (lo < len && s_col[grp][lo] == col) return lo;
-    *A.error = 1;
-    return -1;
-  };
+  auto find_slot = [&](int32_t col) { return sorted_slot(s_col[grp], len, col, A.error); };
   // add one item of NC columns to the row; `sl` holds the CSR slot of each column
   auto add_item = [&](auto nc_tag, bool has, const int32_t* cols, double* acc, const int* sl)
   {
@@ -1410,25 +1563,7 @@ __global__ void __launch_bounds__(kWave, DEG > 1 ? (CUTS ? (CUTT ? (STD ? 3 : 4)
       const bool bc = has && (row_bc || (A.bc1 != nullptr && A.bc1[cols[j]] != 0));
       v[j] = bc ? 0.0 : acc[j];
     }
-    if constexpr (ORDERED)
-    {
-      for (int turn = 0; turn < G; ++turn) // one lane of each group at a time: item order
-      {
-        if (gl == turn)
-        {
-#pragma unroll
-          for (int j = 0; j < NC; ++j)
-            if (s[j] >= 0) s_val[grp][s[j]] += v[j];
-        }
-        __syncthreads(); // block = one wavefront: orders the LDS read-modify-writes of successive turns
-      }
-    }
-    else
-    {
-#pragma unroll
-      for (int j = 0; j < NC; ++j)
-        if (s[j] >= 0) atomicAdd(&s_val[grp][s[j]], v[j]);
-    }
+    row_add<ORDERED, G, NC>(s_val[grp], gl, s, v);
   };
 
   // ---- cell items, R per lane per pass.  The index loads of a pass (incidence
@@ -1847,31 +1982,7 @@ __global__ void __launch_bounds__(kWave, DEG > 1 ? (CUTS ? (CUTT ? (STD ? 3 : 4)
     }
   }
   __syncthreads();
-  if (A.fresh == 2)
-  {
-    // first and only writer of these rows on a matrix that holds nothing yet (set_value(0) fused): stored
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q)
-    {
-      const int k = gl + q * G;
-      if (k < len) A.values[rb + k] = s_val[grp][k];
-    }
-    return;
-  }
-  // Row epilogue: values[row] += reduced row, loads batched
-  double myval[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    myval[q] = k < len ? A.values[rb + k] : 0.0;
-  }
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    if (k < len) A.values[rb + k] = myval[q] + s_val[grp][k];
-  }
+  row_writeback<G, KMAX>(A.values, rb, len, gl, s_val[grp], A.fresh == 2);
 }
 
 // ---------------------------------------------------------------------------
@@ -1899,19 +2010,13 @@ __global__ void __launch_bounds__(kWave, CFX_IFC_WAVES) assemble_rows_p2_interfa
   // compare steps -- 24 lookups per pass were 770 of the ~1000 VALU instructions of a pass, and the kernel's VALU
   // issue alone was half its run time (profiles/r03: 2964 VALU wave-instructions per wavefront)
   constexpr int HS = 2 * CAP;
-  static_assert((HS & (HS - 1)) == 0, "power of two");
-  constexpr int kHashShift = HS == 128 ? 25 : (HS == 256 ? 24 : (HS == 512 ? 23 : 22)); // multiplicative hash: the top log2(HS) bits
-  static_assert(HS == 128 || HS == 256 || HS == 512 || HS == 1024, "hash shift");
   __shared__ int32_t s_key[RPW][HS];
   __shared__ uint16_t s_slot[RPW][HS];
   __shared__ double s_val[RPW][CAP + 1];
-  const int lane = threadIdx.x, grp = lane / G, gl = lane % G;
-  const int64_t ri = CFX_ROW_BLOCK * RPW + grp;
-  const bool live = ri < dev_n(A.n_active);
-  const int64_t r = live ? A.active_rows[ri] : 0;
-  const int64_t rb = live ? A.indptr[r] : 0;
-  int len = live ? (int)(A.indptr[r + 1] - rb) : 0;
-  if (len > CAP) { *A.error = 2; len = 0; }
+  const RowHead H = row_head<G, CAP>(dev_n(A.n_active), A.active_rows, A.indptr, A.error);
+  const int grp = H.grp, gl = H.gl, len = H.len;
+  const bool live = H.live;
+  const int64_t r = H.r, rb = H.rb;
   const int64_t cb = live ? A.d2c_off[r] : 0;
   const int nc = (live && len > 0) ? (int)(A.d2c_off[r + 1] - cb) : 0;
   const bool facets = live && len > 0 && A.d2f_off != nullptr;
@@ -1936,9 +2041,7 @@ __global__ void __launch_bounds__(kWave, CFX_IFC_WAVES) assemble_rows_p2_interfa
       if (k < len)
       {
         s_val[grp][k] = 0.0;
-        unsigned h = ((uint32_t)mycol[q] * 2654435761u) >> kHashShift;
-        while (atomicCAS(&s_key[grp][h], -1, mycol[q]) != -1) h = (h + 1) & (HS - 1); // (columns of a row are distinct)
-        s_slot[grp][h] = (uint16_t)k;
+        RowHash<HS>::insert(s_key[grp], s_slot[grp], mycol[q], k);
       }
     }
   }
@@ -1946,30 +2049,7 @@ __global__ void __launch_bounds__(kWave, CFX_IFC_WAVES) assemble_rows_p2_interfa
   const bool row_bc = live && A.bc0 && A.bc0[r];
   const bool diag_bc = row_bc || (live && A.bc1 != nullptr && A.bc1[r] != 0);
   double dsum = 0.0;
-  auto find_slot = [&](int32_t col) -> int
-  {
-    // the first two positions without a branch (load factor <= 1/2: ~9 of 10 lookups end there), both keys in flight
-    // together; the probe loop only behind them (26 loops with data-dependent trip counts per pass were a good part
-    // of the kernel's scalar instructions: as many as vector ones)
-    const unsigned h0 = ((uint32_t)col * 2654435761u) >> kHashShift, h1 = (h0 + 1) & (HS - 1);
-    const int32_t k0 = s_key[grp][h0], k1 = s_key[grp][h1];
-    const int v0 = s_slot[grp][h0], v1 = s_slot[grp][h1]; // (requested with the keys: no dependent LDS read on a hit)
-    if (k0 == col) return v0;
-    if (k1 == col) return v1;
-    if (k0 != -1 && k1 != -1)
-    {
-      unsigned h = (h1 + 1) & (HS - 1);
-      for (int probe = 2; probe < HS; ++probe)
-      {
-        const int32_t key = s_key[grp][h];
-        if (key == col) return (int)s_slot[grp][h];
-        if (key == -1) break;
-        h = (h + 1) & (HS - 1);
-      }
-    }
-    *A.error = 1;
-    return -1;
-  };
+  auto find_slot = [&](int32_t col) { return RowHash<HS>::lookup(s_key[grp], s_slot[grp], col, A.error); };
   auto add_item = [&](auto nc_tag, bool has, const int32_t* cols, const double* acc, const int* sl)
   {
     constexpr int NC = decltype(nc_tag)::value;
@@ -2150,29 +2230,7 @@ __global__ void __launch_bounds__(kWave, CFX_IFC_WAVES) assemble_rows_p2_interfa
     }
   }
   __syncthreads();
-  if (A.fresh == 2)
-  {
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q)
-    {
-      const int k = gl + q * G;
-      if (k < len) A.values[rb + k] = s_val[grp][k];
-    }
-    return;
-  }
-  double myval[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    myval[q] = k < len ? A.values[rb + k] : 0.0;
-  }
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    if (k < len) A.values[rb + k] = myval[q] + s_val[grp][k];
-  }
+  row_writeback<G, KMAX>(A.values, rb, len, gl, s_val[grp], A.fresh == 2);
 }
 
 // ---------------------------------------------------------------------------
@@ -2197,29 +2255,12 @@ __global__ void __launch_bounds__(kWave, CFX_P1_WAVES) assemble_rows_p1_kernel(R
   constexpr int RPW = kWave / G;
   __shared__ int32_t s_col[RPW][CAP + 1];
   __shared__ double s_val[RPW][CAP + 1];
-  const int lane = threadIdx.x, grp = lane / G, gl = lane % G;
-  const int64_t ri = CFX_ROW_BLOCK * RPW + grp;
-  const bool live = ri < dev_n(A.n_active);
-  const int64_t r = live ? A.active_rows[ri] : 0;
-  const int64_t rb = live ? A.indptr[r] : 0;
-  int len = live ? (int)(A.indptr[r + 1] - rb) : 0;
-  if (len > CAP) { *A.error = 2; len = 0; }
+  const RowHead H = row_head<G, CAP>(dev_n(A.n_active), A.active_rows, A.indptr, A.error);
+  const int grp = H.grp, gl = H.gl, len = H.len;
+  const bool live = H.live;
+  const int64_t r = H.r, rb = H.rb;
   constexpr int KMAX = CAP / G;
-  {
-    int32_t mycol[KMAX];
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q)
-    {
-      const int k = gl + q * G;
-      mycol[q] = k < len ? A.indices[rb + k] : -1;
-    }
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q)
-    {
-      const int k = gl + q * G;
-      if (k < len) { s_col[grp][k] = mycol[q]; s_val[grp][k] = 0.0; }
-    }
-  }
+  stage_row_columns<G, KMAX>(A.indices, rb, len, gl, s_col[grp], s_val[grp]);
   __syncthreads();
   const int64_t cb = live ? A.d2c_off[r] : 0;
   const int nc = (live && len > 0) ? (int)(A.d2c_off[r + 1] - cb) : 0;
@@ -2230,19 +2271,7 @@ __global__ void __launch_bounds__(kWave, CFX_P1_WAVES) assemble_rows_p1_kernel(R
   for (int d = 0; d < TDIM; ++d) xr[d] = 0.0;
   if (live) load_vertex<TDIM>(A.x, r, xr);
   double dsum = 0.0;
-
-  auto find_slot = [&](int32_t col) -> int
-  {
-    int lo = 0, hi = len;
-    while (lo < hi)
-    {
-      const int mid = (lo + hi) >> 1;
-      if (s_col[grp][mid] < col) lo = mid + 1; else hi = mid;
-    }
-    if (lo < len && s_col[grp][lo] == col) return lo;
-    *A.error = 1;
-    return -1;
-  };
+  auto find_slot = [&](int32_t col) { return sorted_slot(s_col[grp], len, col, A.error); };
 
   constexpr int R = 3; // 3 x 8 lanes cover the 24 tets around a Kuhn-mesh vertex in one pass
   for (int base = 0;; base += R * G)
@@ -2262,17 +2291,7 @@ __global__ void __launch_bounds__(kWave, CFX_P1_WAVES) assemble_rows_p1_kernel(R
 #pragma unroll
     for (int k = 0; k < R; ++k)
     {
-      if (!rep[k]) continue;
-      if constexpr (ND == 4)
-      {
-        const int4 v = *reinterpret_cast<const int4*>(A.dofmap + (int64_t)cell[k] * 4);
-        cd[k][0] = v.x; cd[k][1] = v.y; cd[k][2] = v.z; cd[k][3] = v.w;
-      }
-      else
-      {
-#pragma unroll
-        for (int j = 0; j < ND; ++j) cd[k][j] = A.dofmap[(int64_t)cell[k] * ND + j];
-      }
+      if (rep[k]) load_dof_row<ND>(A.dofmap, cell[k], cd[k]);
     }
 #pragma unroll
     for (int k = 0; k < R; ++k)
@@ -2301,25 +2320,7 @@ __global__ void __launch_bounds__(kWave, CFX_P1_WAVES) assemble_rows_p1_kernel(R
         for (int t = 0; t < TDIM; ++t)
           ov[t] = (row_bc || (A.bc1 != nullptr && A.bc1[oc[t]] != 0)) ? 0.0 : off[t] * scale;
       }
-      if constexpr (ORDERED)
-      {
-        for (int turn = 0; turn < G; ++turn) // one lane of each group at a time: item order
-        {
-          if (gl == turn)
-          {
-#pragma unroll
-            for (int t = 0; t < TDIM; ++t)
-              if (osl[t] >= 0) s_val[grp][osl[t]] += ov[t];
-          }
-          __syncthreads();
-        }
-      }
-      else
-      {
-#pragma unroll
-        for (int t = 0; t < TDIM; ++t)
-          if (osl[t] >= 0) atomicAdd(&s_val[grp][osl[t]], ov[t]);
-      }
+      row_add<ORDERED, G, TDIM>(s_val[grp], gl, osl, ov);
     }
   }
   {
@@ -2333,31 +2334,9 @@ __global__ void __launch_bounds__(kWave, CFX_P1_WAVES) assemble_rows_p1_kernel(R
     }
   }
   __syncthreads();
-  if (A.fresh == 2)
-  {
-    // first writer of these rows on a matrix that holds nothing yet (set_value(0) fused, run_matrix): stored -- the
-    // zero fill skipped them, the rule / facet items are added by the kernel that follows
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q)
-    {
-      const int k = gl + q * G;
-      if (k < len) A.values[rb + k] = s_val[grp][k];
-    }
-    return;
-  }
-  double myval[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    myval[q] = k < len ? A.values[rb + k] : 0.0;
-  }
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    if (k < len) A.values[rb + k] = myval[q] + s_val[grp][k];
-  }
+  // fresh == 2: first writer of these rows on a matrix that holds nothing yet (set_value(0) fused, run_matrix) -- the
+  // zero fill skipped them, the rule / facet items are added by the kernel that follows
+  row_writeback<G, KMAX>(A.values, rb, len, gl, s_val[grp], A.fresh == 2);
 }
 
 // ---------------------------------------------------------------------------
@@ -2392,13 +2371,11 @@ __global__ void __launch_bounds__(kWave, CFX_PLAIN_WAVES) assemble_rows_plain_ke
   constexpr int SX = CAP <= 32 ? CAP : 32; // staged stencil entries per row (a plain row is no longer than its stencil)
   __shared__ double s_val[RPW][CAP + 1];
   __shared__ double s_x[STAGE ? RPW : 1][STAGE ? SX + 1 : 1][TDIM];
-  const int lane = threadIdx.x, grp = lane / G, gl = lane % G;
-  const int64_t ri = CFX_ROW_BLOCK * RPW + grp;
-  const bool live = ri < dev_n(A.n_active);
-  const int64_t r = live ? A.active_rows[ri] : 0;
-  const int64_t rb = live ? A.indptr[r] : 0;
-  int len = live ? (int)(A.indptr[r + 1] - rb) : 0;
-  if (len > CAP) { *A.error = 2; len = 0; }
+  const RowHead H = row_head<G, CAP>(dev_n(A.n_active), A.active_rows, A.indptr, A.error);
+  const int grp = H.grp, gl = H.gl;
+  const bool live = H.live;
+  const int64_t ri = H.ri, r = H.r, rb = H.rb;
+  int len = H.len;
 #pragma unroll
   for (int q = 0; q < KMAX; ++q)
   {
@@ -2492,17 +2469,7 @@ __global__ void __launch_bounds__(kWave, CFX_PLAIN_WAVES) assemble_rows_plain_ke
 #pragma unroll
       for (int k = 0; k < R; ++k)
       {
-        if (!rep[k]) continue;
-        if constexpr (ND == 4)
-        {
-          const int4 v = *reinterpret_cast<const int4*>(A.dofmap + (int64_t)cell[k] * 4);
-          cd[k][0] = v.x; cd[k][1] = v.y; cd[k][2] = v.z; cd[k][3] = v.w;
-        }
-        else
-        {
-#pragma unroll
-          for (int j = 0; j < ND; ++j) cd[k][j] = A.dofmap[(int64_t)cell[k] * ND + j];
-        }
+        if (rep[k]) load_dof_row<ND>(A.dofmap, cell[k], cd[k]);
       }
     }
 #pragma unroll
@@ -2548,25 +2515,7 @@ __global__ void __launch_bounds__(kWave, CFX_PLAIN_WAVES) assemble_rows_plain_ke
         for (int t = 0; t < TDIM; ++t)
           ov[t] = (row_bc || (A.bc1 != nullptr && A.bc1[oc[t]] != 0)) ? 0.0 : off[t] * scale;
       }
-      if constexpr (ORDERED)
-      {
-        for (int turn = 0; turn < G; ++turn) // one lane of each group at a time: item order
-        {
-          if (gl == turn)
-          {
-#pragma unroll
-            for (int t = 0; t < TDIM; ++t)
-              if (osl[t] >= 0) s_val[grp][osl[t]] += ov[t];
-          }
-          __syncthreads();
-        }
-      }
-      else
-      {
-#pragma unroll
-        for (int t = 0; t < TDIM; ++t)
-          if (osl[t] >= 0) atomicAdd(&s_val[grp][osl[t]], ov[t]);
-      }
+      row_add<ORDERED, G, TDIM>(s_val[grp], gl, osl, ov);
     }
   }
   {
@@ -2576,30 +2525,8 @@ __global__ void __launch_bounds__(kWave, CFX_PLAIN_WAVES) assemble_rows_plain_ke
     if (gl == 0 && nc > 0 && len > 0) atomicAdd(&s_val[grp][__popcll(mask & ((1ull << dpos) - 1ull))], d);
   }
   __syncthreads();
-  if (A.fresh)
-  {
-    // `values` was zeroed by this very call (cfx_assemble_matrix_zeroed) and a plain row has one writer: store
-#pragma unroll
-    for (int q = 0; q < KMAX; ++q)
-    {
-      const int k = gl + q * G;
-      if (k < len) A.values[rb + k] = s_val[grp][k];
-    }
-    return;
-  }
-  double myval[KMAX];
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    myval[q] = k < len ? A.values[rb + k] : 0.0;
-  }
-#pragma unroll
-  for (int q = 0; q < KMAX; ++q)
-  {
-    const int k = gl + q * G;
-    if (k < len) A.values[rb + k] = myval[q] + s_val[grp][k];
-  }
+  // fresh: `values` was zeroed by this very call (cfx_assemble_matrix_zeroed) and a plain row has one writer: store
+  row_writeback<G, KMAX>(A.values, rb, len, gl, s_val[grp], A.fresh != 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -2990,18 +2917,7 @@ __global__ void __launch_bounds__(kWave, CFX_BLOCK_WAVES) assemble_rows_block_ke
   const int64_t cb = cells ? A.d2c_off[r] : 0;
   const int nc = cells ? (int)(A.d2c_off[r + 1] - cb) : 0;
   const bool row_bc = live && A.bc0 && A.bc0[R];
-  auto find_slot = [&](int32_t col) -> int
-  {
-    int lo = 0, hi = len;
-    while (lo < hi)
-    {
-      const int mid = (lo + hi) >> 1;
-      if (s_col[grp][mid] < col) lo = mid + 1; else hi = mid;
-    }
-    if (lo < len && s_col[grp][lo] == col) return lo;
-    *A.error = 1;
-    return -1;
-  };
+  auto find_slot = [&](int32_t col) { return sorted_slot(s_col[grp], len, col, A.error); };
   for (int base = 0;; base += G)
   {
     if (__ballot(base + gl < nc) == 0) break;
@@ -3388,6 +3304,15 @@ bool deterministic()
   return env_is<Sw::DETERMINISTIC>('1');
 }
 
+// launch of a row kernel that is compiled with and without the lane-ordered reduction: pick(tag) names the
+// instantiation whose ORDERED argument is decltype(tag)::value
+template <typename Pick, typename... Args>
+inline void launch_ordered(bool det, const char* name, Pick pick, dim3 grid, Args... args)
+{
+  if (det) launch(name, pick(std::true_type{}), grid, dim3(kWave), 0, args...);
+  else launch(name, pick(std::false_type{}), grid, dim3(kWave), 0, args...);
+}
+
 // stage 2, bilinear forms, degree 2: the rows that copied their static neighbour list (cfx_pattern_s::full_rows --
 // every incident cell an uncut entity of the one stiffness integral).  An item = incidence entry + its 12-byte
 // slot record (cfx::Stencil::slotn): no marks, no dofmap row, no column search, no staged tensor -- the row of the
@@ -3416,13 +3341,10 @@ __global__ void __launch_bounds__(kWave, CFX_P2PLAIN_WAVES) assemble_rows_p2_pla
 {
   constexpr int ND = Elem<TDIM, 2>::ND, RPW = kWave / G;
   __shared__ double s_val[RPW][CAP];
-  const int lane = threadIdx.x, grp = lane / G, gl = lane % G;
-  const int64_t ri = CFX_ROW_BLOCK * RPW + grp;
-  const bool live = ri < A.n;
-  const int64_t r = live ? A.rows[ri] : 0;
-  const int64_t rb = live ? A.indptr[r] : 0;
-  int len = live ? (int)(A.indptr[r + 1] - rb) : 0;
-  if (len > CAP) { *A.error = 2; len = 0; }
+  const RowHead H = row_head<G, CAP>(A.n, A.rows, A.indptr, A.error);
+  const int grp = H.grp, gl = H.gl, len = H.len;
+  const bool live = H.live;
+  const int64_t r = H.r, rb = H.rb;
   for (int k = gl; k < len; k += G) s_val[grp][k] = 0.0;
   __syncthreads();
   const int64_t cb = live ? A.d2c_off[r] : 0;
@@ -3453,25 +3375,7 @@ __global__ void __launch_bounds__(kWave, CFX_P2PLAIN_WAVES) assemble_rows_p2_pla
       const uint32_t w = j < 4 ? w0 : (j < 8 ? w1 : w2);
       sl[j] = has ? (int)((w >> (8 * (j & 3))) & 0xffu) : -1;
     }
-    if constexpr (ORDERED)
-    {
-      for (int turn = 0; turn < G; ++turn)
-      {
-        if (gl == turn)
-        {
-#pragma unroll
-          for (int j = 0; j < ND; ++j)
-            if (sl[j] >= 0) s_val[grp][sl[j]] += acc[j];
-        }
-        __syncthreads();
-      }
-    }
-    else
-    {
-#pragma unroll
-      for (int j = 0; j < ND; ++j)
-        if (sl[j] >= 0) atomicAdd(&s_val[grp][sl[j]], acc[j]);
-    }
+    row_add<ORDERED, G, ND>(s_val[grp], gl, sl, acc);
   }
   __syncthreads();
   if (A.fresh)
@@ -4549,6 +4453,22 @@ inline bool p1_cut_combine_ok(const cfx_form_s* a, const cfx_row_plan& plan)
   return n >= 2;
 }
 
+// where a kernel finds the rules of a cell in cell slot s of the plan: the sorted parents of the integral's rules and
+// the plan's hash cell -> first rule
+template <typename Slot>
+inline void set_rule_lookup(Slot& S, const cfx_row_plan& plan, int s, const cfx_integral_dev& I)
+{
+  S.parent_map = I.rules->parent_map.p;
+  S.rule_keys = plan.rule_keys[s].p; S.rule_first = plan.rule_first[s].p; S.rule_mask = plan.rule_mask[s];
+}
+
+// the points of the runtime rules of integral I, for the kernels that integrate over them (CutSlot, CombineSlot, Rect2Slot)
+template <typename Slot>
+inline void set_rule_points(Slot& S, const cfx_integral_dev& I)
+{
+  S.offsets = I.rules->offsets.p; S.points = I.rules->points.p; S.weights = I.rules->weights.p;
+}
+
 template <int TDIM, int DEG, int BS = 1>
 RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
 {
@@ -4616,16 +4536,14 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
         vec_tensors<TDIM, DEG>(a, I, false, st.buffers.back().p, st.vec_t2, by_cell ? V->mesh->ncells : 0, st.lat_src, s);
     }
     const int64_t n_rules = I.rules ? I.rules->nr.cap() : 0;
-    if (n_rules > 0 && combine_cuts)
+    if (n_rules > 0)
     {
-      // (the rule lookups stay valid for the kernels that ask for them; nothing is staged per integral)
-      R.parent_map = I.rules->parent_map.p; R.nr = rule_bound(I.rules);
-      R.rule_keys = plan.rule_keys[s].p; R.rule_first = plan.rule_first[s].p; R.rule_mask = plan.rule_mask[s];
+      set_rule_lookup(R, plan, s, I);
+      R.nr = rule_bound(I.rules);
     }
-    else if (n_rules > 0)
+    // (combine_cuts: the rule lookups stay valid for the kernels that ask for them; nothing is staged per integral)
+    if (n_rules > 0 && !combine_cuts)
     {
-      R.parent_map = I.rules->parent_map.p; R.nr = rule_bound(I.rules);
-      R.rule_keys = plan.rule_keys[s].p; R.rule_first = plan.rule_first[s].p; R.rule_mask = plan.rule_mask[s];
       const bool moments = DEG == 2 && BS == 1 && a->rank == 2 && I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0
                            && env_on<Sw::P2_MOMENTS>();
       st.buffers.emplace_back(n_rules * (moments ? 16 : tsize));
@@ -4649,11 +4567,11 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
         CombineSlot& S = C.slot[s];
         C.start[s + 1] = C.start[s];
         if (!A.cell[s].rule_tensors) continue;
-        const cfx_rules_s* R = I.rules;
         S.kernel = I.kernel; S.point_stride = I.point_stride;
         for (int k = 0; k < 3; ++k) S.params[k] = I.params[k];
-        S.offsets = R->offsets.p; S.parent_map = R->parent_map.p; S.n = R->nr.devn(); S.bound = rule_bound(R);
-        S.points = R->points.p; S.weights = R->weights.p; S.point_data = I.point_data.n > 0 ? I.point_data.p : nullptr;
+        set_rule_points(S, I);
+        S.point_data = I.point_data.n > 0 ? I.point_data.p : nullptr;
+        S.parent_map = I.rules->parent_map.p; S.n = I.rules->nr.devn(); S.bound = rule_bound(I.rules);
         S.keys = plan.rule_keys[s].p; S.first = plan.rule_first[s].p; S.mask = plan.rule_mask[s];
         S.out = const_cast<double*>(A.cell[s].rule_tensors);
         C.start[s + 1] += (S.n.cap * kCombineLanes + kBlock - 1) / kBlock * kBlock;
@@ -4679,10 +4597,10 @@ RowArgs prepare(cfx_form_s* a, Stage1& st, bool combine_cuts = false)
           S.kernel = I.kernel; S.point_stride = I.point_stride; S.params[0] = I.params[0]; S.params[1] = I.params[1];
           if (I.rules && I.rules->nr.value() > 0)
           {
-            S.offsets = I.rules->offsets.p; S.parent_map = I.rules->parent_map.p; S.nr = I.rules->nr.value();
-            S.points = I.rules->points.p; S.weights = I.rules->weights.p;
+            set_rule_points(S, I);
             S.point_data = I.point_data.n > 0 ? I.point_data.p : nullptr;
-            S.rule_keys = plan.rule_keys[s].p; S.rule_first = plan.rule_first[s].p; S.rule_mask = plan.rule_mask[s];
+            set_rule_lookup(S, plan, s, I);
+            S.nr = I.rules->nr.value();
             S.cut_first = plan.cut_first[s].p;
           }
         }
@@ -4766,6 +4684,14 @@ inline void raise_gather_error(int err)
   require(err == 0, CFX_ERR_RUNTIME, "assemble_matrix: the row gather reported an error");
 }
 
+// assemble_rows_kernel over the rows of Q: G lanes per row, CAP columns
+template <int TDIM, int DEG, int G, int CAP, bool CUTS = true, bool STD = true, bool CUTT = false>
+void launch_rows(bool det, const char* name, const RowArgs& Q)
+{
+  launch_ordered(det, name, [](auto o) { return assemble_rows_kernel<TDIM, DEG, G, CAP, decltype(o)::value, CUTS, STD, CUTT>; },
+                 row_grid((Q.n_active.cap + (kWave / G) - 1) / (kWave / G)), Q);
+}
+
 template <int TDIM, int DEG>
 int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t* bc1, double* values, bool fresh)
 {
@@ -4805,13 +4731,6 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
     const bool det = deterministic();
     const int mr = P->max_row_len;
     cfx_row_plan& plan = row_plan(a);
-#define CFX_ROWS(GG, CAPP, NAME, ARGS)                                                                    \
-  do                                                                                                      \
-  {                                                                                                       \
-    const dim3 grid = row_grid(((ARGS).n_active.cap + (kWave / GG) - 1) / (kWave / GG));                  \
-    if (det) launch(NAME, assemble_rows_kernel<TDIM, DEG, GG, CAPP, true>, grid, dim3(kWave), 0, ARGS);   \
-    else launch(NAME, assemble_rows_kernel<TDIM, DEG, GG, CAPP, false>, grid, dim3(kWave), 0, ARGS);      \
-  } while (0)
     // P1 space on the geometry dofmap whose uncut-cell integrals are all inline stiffness:
     // lean kernel for the uncut items of every row, generic kernel for the rule / facet
     // items of the rows next to the interface
@@ -4882,60 +4801,39 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
             const dim3 gt = T.stream_blocks ? dim3(T.stream_blocks + (tile_blocks > 0 ? row_grid(tile_blocks).x : 0u))
                                             : row_grid(tile_blocks);
             if (tcls == 0)
-            {
-              if (det) launch("assemble_tiles_plain", assemble_tiles_plain_kernel<TDIM, true, 0>, gt, dim3(kWave), 0, T);
-              else launch("assemble_tiles_plain", assemble_tiles_plain_kernel<TDIM, false, 0>, gt, dim3(kWave), 0, T);
-            }
+              launch_ordered(det, "assemble_tiles_plain", [](auto o) { return assemble_tiles_plain_kernel<TDIM, decltype(o)::value, 0>; }, gt, T);
             else
-            {
-              if (det) launch("assemble_tiles_plain", assemble_tiles_plain_kernel<TDIM, true, 1>, gt, dim3(kWave), 0, T);
-              else launch("assemble_tiles_plain", assemble_tiles_plain_kernel<TDIM, false, 1>, gt, dim3(kWave), 0, T);
-            }
+              launch_ordered(det, "assemble_tiles_plain", [](auto o) { return assemble_tiles_plain_kernel<TDIM, decltype(o)::value, 1>; }, gt, T);
           }
           const dim3 gq = row_grid((Q.n_active.cap + (kWave / CFX_PLAIN_G) - 1) / (kWave / CFX_PLAIN_G));
           const bool stage = stn.max_len <= 32 && env_on<Sw::PLAIN_STAGE>();
           // plain rows are subsets of their stencil: the LDS footprint follows the longest stencil
           // (16 covers the 15-vertex stencil of Kuhn meshes: 4.4 KB per block instead of 8.4 KB)
           const int plain_cap = stn.max_len <= 16 ? 16 : (stn.max_len <= 32 ? 32 : 64);
-#define CFX_PLAIN(CAPP)                                                                                                \
-  do                                                                                                                   \
-  {                                                                                                                    \
-    if (det && stage) launch("assemble_rows_plain", assemble_rows_plain_kernel<TDIM, CFX_PLAIN_G, CAPP, true, true>, gq, dim3(kWave), 0, Q);   \
-    else if (det) launch("assemble_rows_plain", assemble_rows_plain_kernel<TDIM, CFX_PLAIN_G, CAPP, true, false>, gq, dim3(kWave), 0, Q);     \
-    else if (stage) launch("assemble_rows_plain", assemble_rows_plain_kernel<TDIM, CFX_PLAIN_G, CAPP, false, true>, gq, dim3(kWave), 0, Q);   \
-    else launch("assemble_rows_plain", assemble_rows_plain_kernel<TDIM, CFX_PLAIN_G, CAPP, false, false>, gq, dim3(kWave), 0, Q);             \
-  } while (0)
+          auto plain = [&](auto cap)
+          {
+            constexpr int CAP = decltype(cap)::value;
+            if (stage) launch_ordered(det, "assemble_rows_plain", [](auto o) { return assemble_rows_plain_kernel<TDIM, CFX_PLAIN_G, CAP, decltype(o)::value, true>; }, gq, Q);
+            else launch_ordered(det, "assemble_rows_plain", [](auto o) { return assemble_rows_plain_kernel<TDIM, CFX_PLAIN_G, CAP, decltype(o)::value, false>; }, gq, Q);
+          };
           if (use_tiles) {}
-          else if (plain_cap == 16) CFX_PLAIN(16); else if (plain_cap == 32) CFX_PLAIN(32); else CFX_PLAIN(64);
-#undef CFX_PLAIN
+          else if (plain_cap == 16) plain(std::integral_constant<int, 16>{});
+          else if (plain_cap == 32) plain(std::integral_constant<int, 32>{});
+          else plain(std::integral_constant<int, 64>{});
           // the uncut items of the interface rows keep the searching kernel
           F.n_active = plan.n_special_rows; F.active_rows = plan.special_rows.p;
         }
         const dim3 grid = row_grid((F.n_active.cap + 7) / 8);
         if (mr <= 32)
-        {
-          if (det) launch("assemble_rows_p1", assemble_rows_p1_kernel<TDIM, 8, 32, true>, grid, dim3(kWave), 0, F);
-          else launch("assemble_rows_p1", assemble_rows_p1_kernel<TDIM, 8, 32, false>, grid, dim3(kWave), 0, F);
-        }
+          launch_ordered(det, "assemble_rows_p1", [](auto o) { return assemble_rows_p1_kernel<TDIM, 8, 32, decltype(o)::value>; }, grid, F);
         else
-        {
-          if (det) launch("assemble_rows_p1", assemble_rows_p1_kernel<TDIM, 8, 64, true>, grid, dim3(kWave), 0, F);
-          else launch("assemble_rows_p1", assemble_rows_p1_kernel<TDIM, 8, 64, false>, grid, dim3(kWave), 0, F);
-        }
+          launch_ordered(det, "assemble_rows_p1", [](auto o) { return assemble_rows_p1_kernel<TDIM, 8, 64, decltype(o)::value>; }, grid, F);
         RowArgs S = A;
         S.n_active = plan.n_special_rows; S.active_rows = plan.special_rows.p; S.mark_mask = 0xF0u;
         if (S.n_active.cap > 0)
         {
-#define CFX_ROWS_CUT(GG, CAPP)                                                                                       \
-  do                                                                                                                 \
-  {                                                                                                                  \
-    const dim3 grid = row_grid((S.n_active.cap + (kWave / GG) - 1) / (kWave / GG));                                  \
-    if (det) launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, GG, CAPP, true, true, false>, grid, dim3(kWave), 0, S);   \
-    else launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, GG, CAPP, false, true, false>, grid, dim3(kWave), 0, S);      \
-  } while (0)
-          if (mr <= 32) CFX_ROWS_CUT(CFX_CUT_G, 32);
-          else CFX_ROWS_CUT(CFX_CUT_G, 64);
-#undef CFX_ROWS_CUT
+          if (mr <= 32) launch_rows<TDIM, DEG, CFX_CUT_G, 32, true, false>(det, "assemble_rows_cut", S);
+          else launch_rows<TDIM, DEG, CFX_CUT_G, 64, true, false>(det, "assemble_rows_cut", S);
         }
       }
     }
@@ -4957,18 +4855,15 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
           && (plan.n_special_rows.value() * 2 <= plan.n_active_rows.value() || env_is<Sw::ROWS_SPLIT>('1')))
       {
         split = true;
-#define CFX_LEAN(GG, CAPP, ROWS, NROWS)                                                                              \
-  do                                                                                                                 \
-  {                                                                                                                  \
-    RowArgs Q = A;                                                                                                   \
-    Q.mark_mask = 0x0Fu; Q.active_rows = (ROWS); Q.n_active = (NROWS); Q.fresh = lazy_zero ? 2 : Q.fresh;           \
-    const dim3 grid = row_grid((Q.n_active.cap + (kWave / GG) - 1) / (kWave / GG));                                  \
-    if (Q.n_active.cap > 0)                                                                                          \
-    {                                                                                                                \
-      if (det) launch("assemble_rows_uncut", assemble_rows_kernel<TDIM, DEG, GG, CAPP, true, false>, grid, dim3(kWave), 0, Q);  \
-      else launch("assemble_rows_uncut", assemble_rows_kernel<TDIM, DEG, GG, CAPP, false, false>, grid, dim3(kWave), 0, Q);     \
-    }                                                                                                                \
-  } while (0)
+        // the lean form (uncut items only) over a list of rows: 16 lanes and 256 columns per row, or 8 and 64 (`narrow`)
+        auto lean = [&](const int32_t* rows, DevN nrows, bool narrow = false)
+        {
+          RowArgs Q = A;
+          Q.mark_mask = 0x0Fu; Q.active_rows = rows; Q.n_active = nrows; Q.fresh = lazy_zero ? 2 : Q.fresh;
+          if (Q.n_active.cap <= 0) return;
+          if (narrow) launch_rows<TDIM, DEG, 8, 64, false>(det, "assemble_rows_uncut", Q);
+          else launch_rows<TDIM, DEG, 16, 256, false>(det, "assemble_rows_uncut", Q);
+        };
         // (decided here, used below: the dedicated interface kernel takes the pattern's short / long lists whole)
         bool lean_ok = one_pass && (plan.nfacets.value() == 0 || (A.fold_facets == 3 && A.facet_tensors != nullptr));
         for (int q = 0; q < A.n_cell; ++q)
@@ -4977,12 +4872,12 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
 
         if (lean_ok) {}
         else if (one_pass)
-          CFX_LEAN(16, 256, P->odd_rows.p, P->n_odd_rows);
+          lean(P->odd_rows.p, P->n_odd_rows);
         else
         {
-          CFX_LEAN(8, 64, P->short_rows.p, P->n_short_rows);
-          CFX_LEAN(16, 256, P->mid_rows.p, P->n_mid_rows);
-          CFX_LEAN(16, 256, P->long_rows.p, P->n_long_rows);
+          lean(P->short_rows.p, P->n_short_rows, true);
+          lean(P->mid_rows.p, P->n_mid_rows);
+          lean(P->long_rows.p, P->n_long_rows);
         }
         if (P->full_plan == plan.serial && P->n_full_rows > 0)
         {
@@ -5000,27 +4895,19 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
             // half its time on VALU issue (geometry + closed-form row per item).  (Splitting the list by row length for a
             // 32-column form of the short rows gains as much here and costs 1.8 ms in the pattern.)
             if (stn.max_len <= 72)
-            {
-              const dim3 grid = row_grid((Q.n + 15) / 16);
-              if (det) launch("assemble_rows_p2_plain", assemble_rows_p2_plain_kernel<TDIM, 4, 72, true>, grid, dim3(kWave), 0, Q);
-              else launch("assemble_rows_p2_plain", assemble_rows_p2_plain_kernel<TDIM, 4, 72, false>, grid, dim3(kWave), 0, Q);
-            }
+              launch_ordered(det, "assemble_rows_p2_plain", [](auto o) { return assemble_rows_p2_plain_kernel<TDIM, 4, 72, decltype(o)::value>; },
+                             row_grid((Q.n + 15) / 16), Q);
             else
-            {
-              const dim3 grid = row_grid((Q.n + 7) / 8);
-              if (det) launch("assemble_rows_p2_plain", assemble_rows_p2_plain_kernel<TDIM, 8, 128, true>, grid, dim3(kWave), 0, Q);
-              else launch("assemble_rows_p2_plain", assemble_rows_p2_plain_kernel<TDIM, 8, 128, false>, grid, dim3(kWave), 0, Q);
-            }
+              launch_ordered(det, "assemble_rows_p2_plain", [](auto o) { return assemble_rows_p2_plain_kernel<TDIM, 8, 128, decltype(o)::value>; },
+                             row_grid((Q.n + 7) / 8), Q);
           }
           else
-            CFX_LEAN(16, 256, P->full_rows.p, P->n_full_rows);
+            lean(P->full_rows.p, P->n_full_rows);
         }
-#undef CFX_LEAN
         RowArgs S = A;
         S.n_active = plan.n_special_rows; S.active_rows = plan.special_rows.p; S.mark_mask = 0xF0u;
         if (S.n_active.cap > 0)
         {
-          const dim3 grid = row_grid((S.n_active.cap + 3) / 4);
           // every uncut-cell integral the closed-form stiffness row, every facet term as rank-one records (or none):
           // the dedicated interface kernel; else the general one
           if (lean_ok)
@@ -5036,50 +4923,35 @@ int run_matrix(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const int8_t*
             const dim3 g1 = row_grid((S1.n_active.cap + 7) / 8), g2 = row_grid((S2.n_active.cap + 3) / 4);
             const dim3 g3 = row_grid((S3.n_active.cap + 3) / 4);
             if (S3.n_active.cap > 0)
-            {
-              if (det) launch("assemble_rows_cut", assemble_rows_p2_interface_kernel<TDIM, 16, 128, true>, g3, dim3(kWave), 0, S3);
-              else launch("assemble_rows_cut", assemble_rows_p2_interface_kernel<TDIM, 16, 128, false>, g3, dim3(kWave), 0, S3);
-            }
+              launch_ordered(det, "assemble_rows_cut", [](auto o) { return assemble_rows_p2_interface_kernel<TDIM, 16, 128, decltype(o)::value>; }, g3, S3);
             if (S1.n_active.cap > 0)
-            {
-              if (det) launch("assemble_rows_cut", assemble_rows_p2_interface_kernel<TDIM, 8, 64, true>, g1, dim3(kWave), 0, S1);
-              else launch("assemble_rows_cut", assemble_rows_p2_interface_kernel<TDIM, 8, 64, false>, g1, dim3(kWave), 0, S1);
-            }
+              launch_ordered(det, "assemble_rows_cut", [](auto o) { return assemble_rows_p2_interface_kernel<TDIM, 8, 64, decltype(o)::value>; }, g1, S1);
             if (S2.n_active.cap > 0)
-            {
-              if (det) launch("assemble_rows_cut", assemble_rows_p2_interface_kernel<TDIM, 16, 256, true>, g2, dim3(kWave), 0, S2);
-              else launch("assemble_rows_cut", assemble_rows_p2_interface_kernel<TDIM, 16, 256, false>, g2, dim3(kWave), 0, S2);
-            }
-
+              launch_ordered(det, "assemble_rows_cut", [](auto o) { return assemble_rows_p2_interface_kernel<TDIM, 16, 256, decltype(o)::value>; }, g2, S2);
           }
           else if (one_pass)
           {
             S.mark_mask = 0xFFu; S.fresh = lazy_zero ? 2 : S.fresh;
-            if (det) launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, 16, 256, true, true, true, true>, grid, dim3(kWave), 0, S);
-            else launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, 16, 256, false, true, true, true>, grid, dim3(kWave), 0, S);
+            launch_rows<TDIM, DEG, 16, 256, true, true, true>(det, "assemble_rows_cut", S);
           }
           else if (combine_cuts && S.cut_tensors)
-          {
-            if (det) launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, 16, 256, true, true, false, true>, grid, dim3(kWave), 0, S);
-            else launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, 16, 256, false, true, false, true>, grid, dim3(kWave), 0, S);
-          }
-          else if (det) launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, 16, 256, true, true, false>, grid, dim3(kWave), 0, S);
-          else launch("assemble_rows_cut", assemble_rows_kernel<TDIM, DEG, 16, 256, false, true, false>, grid, dim3(kWave), 0, S);
+            launch_rows<TDIM, DEG, 16, 256, true, false, true>(det, "assemble_rows_cut", S);
+          else
+            launch_rows<TDIM, DEG, 16, 256, true, false>(det, "assemble_rows_cut", S);
         }
       }
     }
     if (!split)
     {
       A.mark_mask = 0xFFu;
-      if (mr <= 32) CFX_ROWS(8, 32, "assemble_rows", A);
-      else if (mr <= 64) CFX_ROWS(8, 64, "assemble_rows", A);
+      if (mr <= 32) launch_rows<TDIM, DEG, 8, 32>(det, "assemble_rows", A);
+      else if (mr <= 64) launch_rows<TDIM, DEG, 8, 64>(det, "assemble_rows", A);
       else if (DEG > 1 && mr <= 256)
       {
-        if constexpr (DEG > 1) CFX_ROWS(16, 256, "assemble_rows", A); // P2 rows: 20-70 columns, up to ~200 with facets
+        if constexpr (DEG > 1) launch_rows<TDIM, DEG, 16, 256>(det, "assemble_rows", A); // P2 rows: 20-70 columns, up to ~200 with facets
       }
-      else CFX_ROWS(64, 512, "assemble_rows_wide", A);
+      else launch_rows<TDIM, DEG, 64, 512>(det, "assemble_rows_wide", A);
     }
-#undef CFX_ROWS
   }
   return err.deferred ? 0 : read_scalar(err.p);
 }
@@ -5120,15 +4992,15 @@ int run_matrix_block(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const i
     const int mr = P->max_row_len; // scalar columns per row
     bool closed = false; // (prepare leaves a block space's uncut integrals staged, 0, or closed-form, 3)
     for (int s = 0; s < A.n_cell; ++s) closed = closed || A.cell[s].std_inline == 3;
-#define CFX_BLOCK_V(GG, CAPP, ORD, INL) \
-  launch("assemble_rows_block", assemble_rows_block_kernel<TDIM, DEG, BS, GG, CAPP, ORD, INL>, grid, dim3(kWave), 0, A)
-#define CFX_BLOCK(GG, CAPP)                                                                                          \
-  do                                                                                                                 \
-  {                                                                                                                  \
-    const dim3 grid = row_grid((A.n_active.cap * BS + (kWave / GG) - 1) / (kWave / GG));                             \
-    if (closed) { if (det) CFX_BLOCK_V(GG, CAPP, true, 2); else CFX_BLOCK_V(GG, CAPP, false, 2); }                   \
-    else { if (det) CFX_BLOCK_V(GG, CAPP, true, 0); else CFX_BLOCK_V(GG, CAPP, false, 0); }                          \
-  } while (0)
+    // assemble_rows_block_kernel over the rows of A: G lanes per row, CAP scalar columns
+    auto block = [&](auto g, auto cap)
+    {
+      constexpr int G = decltype(g)::value, CAP = decltype(cap)::value;
+      const dim3 grid = row_grid((A.n_active.cap * BS + (kWave / G) - 1) / (kWave / G));
+      if (closed) launch_ordered(det, "assemble_rows_block", [](auto o) { return assemble_rows_block_kernel<TDIM, DEG, BS, G, CAP, decltype(o)::value, 2>; }, grid, A);
+      else launch_ordered(det, "assemble_rows_block", [](auto o) { return assemble_rows_block_kernel<TDIM, DEG, BS, G, CAP, decltype(o)::value, 0>; }, grid, A);
+    };
+    using std::integral_constant;
     // degree 2: the dofs whose rows copied their static list, all BS component rows at a time
     if constexpr (DEG == 2)
     {
@@ -5181,12 +5053,10 @@ int run_matrix_block(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, const i
     }
     if (A.n_active.cap > 0)
     {
-    if (mr <= 32) CFX_BLOCK(8, 32);
-    else if (mr <= 128) CFX_BLOCK(16, 128);
-    else CFX_BLOCK(32, 256);
+    if (mr <= 32) block(integral_constant<int, 8>{}, integral_constant<int, 32>{});
+    else if (mr <= 128) block(integral_constant<int, 16>{}, integral_constant<int, 128>{});
+    else block(integral_constant<int, 32>{}, integral_constant<int, 256>{});
     }
-#undef CFX_BLOCK_V
-#undef CFX_BLOCK
   }
   return err.deferred ? 0 : read_scalar(err.p);
 }
@@ -5695,13 +5565,7 @@ __global__ void __launch_bounds__(kWave) assemble_rows2_kernel(Rect2Args A)
       if (mark && j < R.nd1)
       {
         const int32_t col0 = R.bs1 * R.dofmap1[c * R.nd1 + j];
-        int lo = 0, hi = len;
-        while (lo < hi)
-        {
-          const int mid = (lo + hi) >> 1;
-          if (s_col[grp][mid] < col0) lo = mid + 1; else hi = mid;
-        }
-        if (lo < len && s_col[grp][lo] == col0) pos[j] = lo; else *A.error = 1;
+        pos[j] = sorted_slot(s_col[grp], len, col0, A.error);
         if (pos[j] >= 0)
         {
 #pragma unroll
@@ -5774,9 +5638,8 @@ bool assemble_rect_rows(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, cons
     {
       S.rule_bit = (uint8_t)(16u << s);
       S.nr = rule_bound(I.rules);
-      S.offsets = I.rules->offsets.p; S.parent_map = I.rules->parent_map.p;
-      S.points = I.rules->points.p; S.weights = I.rules->weights.p;
-      S.rule_keys = plan.rule_keys[s].p; S.rule_first = plan.rule_first[s].p; S.rule_mask = plan.rule_mask[s];
+      set_rule_points(S, I);
+      set_rule_lookup(S, plan, s, I);
     }
     if (user_integrand_known(I.kernel))
     {
@@ -5802,15 +5665,9 @@ bool assemble_rect_rows(cfx_form_s* a, cfx_pattern_s* P, const int8_t* bc0, cons
   const dim3 grid = row_grid((nrows_cap + 3) / 4);
   const bool det = deterministic();
   if (V0->mesh->tdim == 2)
-  {
-    if (det) launch("assemble_rows2", assemble_rows2_kernel<2, true>, grid, dim3(kWave), 0, A);
-    else launch("assemble_rows2", assemble_rows2_kernel<2, false>, grid, dim3(kWave), 0, A);
-  }
+    launch_ordered(det, "assemble_rows2", [](auto o) { return assemble_rows2_kernel<2, decltype(o)::value>; }, grid, A);
   else
-  {
-    if (det) launch("assemble_rows2", assemble_rows2_kernel<3, true>, grid, dim3(kWave), 0, A);
-    else launch("assemble_rows2", assemble_rows2_kernel<3, false>, grid, dim3(kWave), 0, A);
-  }
+    launch_ordered(det, "assemble_rows2", [](auto o) { return assemble_rows2_kernel<3, decltype(o)::value>; }, grid, A);
   return true;
 }
 
