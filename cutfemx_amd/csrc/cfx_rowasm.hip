@@ -2707,6 +2707,17 @@ cfx_row_plan& row_plan(cfx_form_s* a)
   return P;
 }
 
+// Whether a staging block of `bytes` is taken: it has to stay below 1 / `fraction` of the card's free memory -- with
+// `count_cached`, of the free memory and what the engine's own block cache would give back
+static bool staging_fits(size_t bytes, size_t fraction, bool count_cached)
+{
+  size_t free_b = 0, total_b = 0;
+  CFX_HIP(hipMemGetInfo(&free_b, &total_b));
+  size_t live_b = 0, cached_b = 0, peak_b = 0;
+  if (count_cached) device_memory_stats(live_b, cached_b, peak_b);
+  return bytes < (free_b + cached_b) / fraction;
+}
+
 const Stencil& space_stencil(cfx_space_s* V)
 {
   Stencil& S = V->stencil;
@@ -2715,17 +2726,19 @@ const Stencil& space_stencil(cfx_space_s* V)
   if (!env_on<Sw::STENCIL>()) return S;
   // P1 scalar space on the geometry dofmap (dofs are mesh vertices): lists + slots; every other space (degree 2,
   // vector-valued, DG): the neighbour lists alone, which is what the sparsity of the plain rows needs
-  if (V->degree != 1 || V->bs != 1 || V->ndofs_cell > 4 || V->dofmap.p != V->mesh->conn.p || V->ndofs != V->mesh->nnodes)
+  const bool lists_only =
+      V->degree != 1 || V->bs != 1 || V->ndofs_cell > 4 || V->dofmap.p != V->mesh->conn.p || V->ndofs != V->mesh->nnodes;
+  if (lists_only && !env_on<Sw::STENCIL_LISTS>()) return S;
+  const Adjacency& adj = V->dof_cells();
+  PatArgs A{};
+  A.n_active = V->ndofs; A.active_rows = nullptr; A.all_cells = 1;
+  A.nd = V->ndofs_cell; A.bs = 1; A.dofmap = V->dofmap.p; // lists of scalar dofs: a block space expands them by bs
+  A.d2c_off = adj.offsets.p; A.d2c = adj.cells.p;
+  DevArray<int32_t> counts(V->ndofs), len(V->ndofs);
+  ZeroFlag overflow, maxlen;
+  A.len = len.p; A.counts = counts.p; A.overflow = overflow.p; A.maxlen = maxlen.p;
+  if (lists_only)
   {
-    if (!env_on<Sw::STENCIL_LISTS>()) return S;
-    const Adjacency& adj = V->dof_cells();
-    PatArgs A{};
-    A.n_active = V->ndofs; A.active_rows = nullptr; A.all_cells = 1;
-    A.nd = V->ndofs_cell; A.bs = 1; A.dofmap = V->dofmap.p; // lists of scalar dofs: a block space expands them by bs
-    A.d2c_off = adj.offsets.p; A.d2c = adj.cells.p;
-    DevArray<int32_t> counts(V->ndofs), len(V->ndofs);
-    ZeroFlag overflow, maxlen;
-    A.len = len.p; A.counts = counts.p; A.overflow = overflow.p; A.maxlen = maxlen.p;
     launch("stencil_rows", pattern_rows_kernel<64, 512>, wave_grid(V->ndofs), dim3(kWave), 0, A);
     if (read_scalar(overflow.p)) return S;
     S.max_len = read_scalar(maxlen.p);
@@ -2738,25 +2751,14 @@ const Stencil& space_stencil(cfx_space_s* V)
     publish_across_lanes();
     return S;
   }
-  const Adjacency& adj = V->dof_cells();
-  PatArgs A{};
-  A.n_active = V->ndofs; A.active_rows = nullptr; A.all_cells = 1;
-  A.nd = V->ndofs_cell; A.bs = 1; A.dofmap = V->dofmap.p;
-  A.d2c_off = adj.offsets.p; A.d2c = adj.cells.p;
-  DevArray<int32_t> counts(V->ndofs), len(V->ndofs);
-  ZeroFlag overflow, maxlen;
-  A.len = len.p; A.counts = counts.p; A.overflow = overflow.p; A.maxlen = maxlen.p;
   // One pass when the card has room for ndofs x 64 staged columns (34 GB at 512^3, released right after): every set is
   // ranked into its staging row and copied once the offsets are known; else count, scan, build every set again and
   // write it in place (30 + 31 ms at 512^3 against 30 + 7).
   DevArray<int32_t> staged;
+  if (staging_fits((size_t)V->ndofs * 64 * sizeof(int32_t), 3, true) && env_on<Sw::STENCIL_STAGED>())
   {
-    size_t free_b = 0, total_b = 0;
-    CFX_HIP(hipMemGetInfo(&free_b, &total_b));
-    size_t live_b = 0, cached_b = 0, peak_b = 0;
-    device_memory_stats(live_b, cached_b, peak_b);
-    const size_t need = (size_t)V->ndofs * 64 * sizeof(int32_t);
-    if (need < (free_b + cached_b) / 3 && env_on<Sw::STENCIL_STAGED>()) { staged.alloc(V->ndofs * 64); A.tmp = staged.p; }
+    staged.alloc(V->ndofs * 64);
+    A.tmp = staged.p;
   }
   launch("stencil_rows", pattern_rows_kernel<4, 64>, wave_grid((V->ndofs + 15) / 16), dim3(kWave), 0, A);
   // The 64-slot set keeps one slot free (a full table cannot be told from an overflowing one): a list of 63 entries, the
@@ -2816,14 +2818,7 @@ const Stencil& space_stencil_tiles(cfx_space_s* V)
       // (the tail of the arena; the permanent tables grow from the front and are checked against it below)
       staged.p = reinterpret_cast<int32_t*>(S.arena.p + ((S.arena.n - need) & ~255LL)); staged.n = ntiles * kTileStage; staged.owned = false;
     }
-    else if (on)
-    {
-      size_t free_b = 0, total_b = 0;
-      CFX_HIP(hipMemGetInfo(&free_b, &total_b));
-      size_t live_b = 0, cached_b = 0, peak_b = 0;
-      device_memory_stats(live_b, cached_b, peak_b);
-      if ((size_t)(need + perm) < (free_b + cached_b) / 3) staged.alloc(ntiles * kTileStage);
-    }
+    else if (on && staging_fits((size_t)(need + perm), 3, true)) staged.alloc(ntiles * kTileStage);
   }
   const uint8_t* tail = (staged.p && !staged.owned) ? reinterpret_cast<const uint8_t*>(staged.p) : nullptr; // arena tail in use
   if (staged.p)
@@ -4088,91 +4083,179 @@ void build_pattern_rectangular(cfx_form_s* a, cfx_pattern_s* P)
   P->built_plan = 0; P->stencil_plan = 0; P->split_plan = 0; P->full_plan = 0; P->odd_plan = 0;
 }
 
-void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
+namespace // build_pattern: the CSR structure of a square form, in six phases
 {
-  if (a->rectangular()) { build_pattern_rectangular(a, P); return; }
-  cfx_space_s* V = a->V;
-  cfx_row_plan& plan = row_plan(a);
-  const Stencil& st = space_stencil(V);
+// "Sublist of rows by predicate": out = [the n_head entries of `head` | src[i] for the i < n with pred(i), in order],
+// compaction and gather under `name`; returns how many were selected.  `idx_keep` takes the selected positions i.
+template <typename Pred>
+int64_t select_rows(const char* name, int64_t n, Pred pred, const int32_t* src, DevArray<int32_t>& out,
+                    DevArray<int32_t>* idx_keep = nullptr, const int32_t* head = nullptr, int64_t n_head = 0)
+{
+  DevArray<int32_t> idx_own;
+  DevArray<int32_t>& idx = idx_keep ? *idx_keep : idx_own;
+  const int64_t m = compact(name, n, pred, idx);
+  out.alloc(n_head + m);
+  if (n_head > 0)
+    CFX_HIP(hipMemcpyAsync(out.p, head, sizeof(int32_t) * (size_t)n_head, hipMemcpyDeviceToDevice, ctx().stream));
+  if (m > 0) launch(name, gather_i32_kernel, grid_for(m), dim3(kBlock), 0, m, idx.p, src, out.p + n_head);
+  return m;
+}
+
+// the cell integrals of a form over a list of uncut entities: how many, and whether each is the closed-form stiffness
+struct UncutIntegrals { int n = 0; bool closed = true; };
+UncutIntegrals uncut_cell_integrals(const cfx_form_s* a)
+{
+  UncutIntegrals u;
+  for (const auto& I : a->integrals)
+    if (I.type == CFX_CELL && I.n_entities.cap() > 0)
+    {
+      ++u.n;
+      u.closed = u.closed && I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0;
+    }
+  return u;
+}
+
+// how the hash sets reach the CSR arrays: copied from `tmp`, from `tmp_short` / `tmp_long`, or built again in place
+enum class HashWrite { None, Staged64, SplitStaged, SplitInPlace, Wide, Huge };
+
+// One build: its phases, and what more than one of them needs under the phase that sets it
+struct PatternBuild
+{
+  cfx_form_s* a;
+  cfx_pattern_s* P;
+  cfx_space_s* V;
+  cfx_row_plan& plan;
+  const Stencil& st;
+  void choose_hashed_rows(), split_reused_rows(), build_hash_sets(), write_columns(), classify_gather_rows();
+  void list_copied_rows(), split_full_rows();
+  bool hash_sets_short_long(), sum_row_offsets();
+  // choose_hashed_rows (rows_h: the n_h rows not written from a mask or a static list; on the stencil path n_h is a
+  // capacity, the plan's count may still be in HBM)
+  bool use_stencil = false, use_lists = false, any_full = false;
+  int64_t n_h = 0, n_special_x = 0, n_plain_x = 0;
+  const int32_t* rows_h = nullptr;
+  DevArray<int32_t> counts, hashed;
+  DevArray<uint8_t> full;
+  // split_reused_rows (rows_d: the n_d rows of rows_h that are hashed in this build)
+  bool reuse = false;
+  int64_t n_d = 0, n_clean = 0;
+  const int32_t* rows_d = nullptr;
+  DevArray<int32_t> dirty_rows, clean_rows;
+  ZeroFlag reuse_maxlen;
+  // build_hash_sets (`deferred`: overflow, longest row and nnz come back in one read-back, in sum_row_offsets)
+  PatArgs S{};
+  DevArray<int32_t> len, tmp, short_rows, long_rows, tmp_short, tmp_long;
+  int64_t n_short = 0, n_long = 0;
+  ZeroFlag overflow, maxlen;
+  HashWrite write = HashWrite::None;
+  bool deferred = false;
+};
+
+void PatternBuild::choose_hashed_rows()
+{
   // plain rows (uncut-cell items only) are subsets of the static stencil: mask + popcount;
   // the hash-set path then only sees the rows next to the interface
-  const bool use_stencil = st.usable && plan.n_plain_rows.cap() > 0 && plan.any_cells;
+  use_stencil = st.usable && plan.n_plain_rows.cap() > 0 && plan.any_cells;
   // lists only (degree 2, vector, DG spaces): the plain rows whose cells are all marked copy their static list
-  const bool use_lists = !st.usable && st.lists && plan.n_plain_rows.cap() > 0 && plan.any_cells;
+  use_lists = !st.usable && st.lists && plan.n_plain_rows.cap() > 0 && plan.any_cells;
   // Row counts that are still in HBM (plan built inside a sync-free step) stay there on the stencil path (P1 on the
   // geometry dofmap), whose kernels take their lengths from the device; the other paths size host-side work by the
   // counts and read them back first.
-  const Count n_h_c = use_stencil ? plan.n_special_rows : Count(plan.n_active_rows.value());
+  n_h = use_stencil ? plan.n_special_rows.cap() : plan.n_active_rows.value();
   if (!use_stencil) { (void)plan.n_special_rows.value(); (void)plan.n_plain_rows.value(); }
-  int64_t n_h = n_h_c.cap();
-  const int64_t n_special_x = plan.n_special_rows.cap(), n_plain_x = plan.n_plain_rows.cap(); // exact off the stencil path
-  const int32_t* rows_h = use_stencil ? plan.special_rows.p : plan.active_rows.p;
+  n_special_x = plan.n_special_rows.cap(); n_plain_x = plan.n_plain_rows.cap(); // exact off the stencil path
+  rows_h = use_stencil ? plan.special_rows.p : plan.active_rows.p;
   P->nrows = V->ndofs * V->bs;
   P->ncols = P->nrows;
-  DevArray<int32_t> counts(P->nrows);
-  DevArray<uint8_t> full;
-  DevArray<int32_t> hashed;
-  bool any_full = false;
-  if (use_lists)
-  {
-    const Adjacency& adj = V->dof_cells();
-    constexpr int G = 4;
-    full.alloc(n_plain_x);
-    launch("pattern_plain_full", plain_full_kernel<G>, dim3((unsigned)((n_plain_x + kWave - 1) / kWave)),
-           dim3(kWave), 0, n_plain_x, plan.plain_rows.p, adj.offsets.p, adj.cells.p, plan.cellmark.p, st.offsets.p,
-           V->bs, full.p, counts.p, plan.bulk ? plan.rowcls.p : (const uint8_t*)nullptr);
-    DevArray<int32_t> odd;
-    const int64_t n_odd = compact("pattern_plain_full", n_plain_x, FlagIsZero{full.p}, odd);
-    any_full = n_odd < n_plain_x;
-    n_h = n_special_x + n_odd;
-    hashed.alloc(n_h);
-    if (n_special_x > 0)
-      CFX_HIP(hipMemcpyAsync(hashed.p, plan.special_rows.p, sizeof(int32_t) * (size_t)n_special_x,
-                             hipMemcpyDeviceToDevice, ctx().stream));
-    if (n_odd > 0)
-      launch("pattern_plain_full", gather_i32_kernel, grid_for(n_odd), dim3(kBlock), 0, n_odd, odd.p, plan.plain_rows.p,
-             hashed.p + n_special_x);
-    rows_h = hashed.p;
-  }
-  // Moving-domain loops: a hashed row whose incident cells kept their signature since the previous pattern of this space
-  // couples the same columns as before -- it copies them (below, once the row offsets are known) instead of building
-  // and ranking its hash set again.  Only the rows around cells that changed go through the hash sets.
-  int64_t n_d = n_h;                 // rows that are hashed in this build
-  const int32_t* rows_d = rows_h;
-  DevArray<int32_t> dirty_rows, clean_rows;
-  int64_t n_clean = 0;
-  ZeroFlag reuse_maxlen;
-  const bool reuse = !use_stencil && n_h > 0 && plan.any_cells && pattern_reuse_ok(a);
+  counts.alloc(P->nrows);
+  if (!use_lists) return;
+  const Adjacency& adj = V->dof_cells();
+  constexpr int G = 4;
+  full.alloc(n_plain_x);
+  launch("pattern_plain_full", plain_full_kernel<G>, dim3((unsigned)((n_plain_x + kWave - 1) / kWave)),
+         dim3(kWave), 0, n_plain_x, plan.plain_rows.p, adj.offsets.p, adj.cells.p, plan.cellmark.p, st.offsets.p,
+         V->bs, full.p, counts.p, plan.bulk ? plan.rowcls.p : (const uint8_t*)nullptr);
+  const int64_t n_odd = select_rows("pattern_plain_full", n_plain_x, FlagIsZero{full.p}, plan.plain_rows.p, hashed,
+                                    nullptr, plan.special_rows.p, n_special_x);
+  any_full = n_odd < n_plain_x;
+  n_h = n_special_x + n_odd;
+  rows_h = hashed.p;
+}
+
+// Moving-domain loops: a hashed row whose incident cells kept their signature since the previous pattern of this space
+// couples the same columns as before -- it copies them (below, once the row offsets are known) instead of building
+// and ranking its hash set again.  Only the rows around cells that changed go through the hash sets.
+void PatternBuild::split_reused_rows()
+{
+  n_d = n_h;                 // rows that are hashed in this build
+  rows_d = rows_h;
+  reuse = !use_stencil && n_h > 0 && plan.any_cells && pattern_reuse_ok(a);
   P->n_hashed_rows = use_stencil ? 0 : n_h;
   P->n_reused_rows = 0;
-  if (reuse)
+  if (!reuse) return;
+  const Adjacency& adj = V->dof_cells();
+  plan_cell_signature(a);
+  const cfx_pattern_cache& pc = V->pcache;
+  const int64_t* prev_indptr = pc.live ? pc.live->indptr.p : pc.indptr.p;
+  DevArray<uint8_t> clean(n_h);
+  launch("pattern_reuse", row_clean_kernel, grid_for(n_h), dim3(kBlock), 0, n_h, rows_h, adj.offsets.p, adj.cells.p,
+         plan.cellsig.p, pc.sig.p, prev_indptr, V->bs, clean.p, counts.p, reuse_maxlen.p);
+  n_d = select_rows("pattern_reuse", n_h, FlagIsZero{clean.p}, rows_h, dirty_rows);
+  n_clean = n_h - n_d;
+  if (n_clean > 0) (void)select_rows("pattern_reuse", n_h, FlagSet8{clean.p}, rows_h, clean_rows);
+  rows_d = dirty_rows.p;
+  P->n_reused_rows = n_clean;
+  if (env_present<Sw::PLAN_DEBUG>())
+    fprintf(stderr, "cutfemx_amd: pattern reuse: %lld of %lld hashed rows copy their columns\n", (long long)n_clean, (long long)n_h);
+}
+
+// lists path: the hashed rows split by the length of their static list -- short rows (the edge dofs of a degree-2
+// space: ~85 % of the rows) take 16 lanes and a 128-slot set, 4 rows per wavefront, the others one wavefront and
+// 512 slots; both count first and build each set again to write it in place.  False: a set overflowed, every row goes wide.
+bool PatternBuild::hash_sets_short_long()
+{
+  constexpr int kShortLen = 40;
+  DevArray<int32_t> short_idx, long_idx;
+  const int64_t* len_of = st.offsets.p;
+  n_short = select_rows("pattern_split", n_d, StaticLenTest{rows_d, len_of, kShortLen, false}, rows_d, short_rows, &short_idx);
+  n_long = n_d - n_short;
+  if (n_long > 0)
+    (void)select_rows("pattern_split", n_d, StaticLenTest{rows_d, len_of, kShortLen, true}, rows_d, long_rows, &long_idx);
+  PatArgs S1 = S, S2 = S;
+  // one pass: every set is ranked into a staging row (128 / 512 columns per row: 6 + 4.5 GB at BASELINE config 4),
+  // copied into the CSR arrays once the row offsets are known -- building each set a second time cost as much again
+  const bool staged_sets = staging_fits(((size_t)n_short * 128 + (size_t)n_long * 512) * sizeof(int32_t), 2, false);
+  if (staged_sets)
   {
-    const Adjacency& adj = V->dof_cells();
-    plan_cell_signature(a);
-    const cfx_pattern_cache& pc = V->pcache;
-    const int64_t* prev_indptr = pc.live ? pc.live->indptr.p : pc.indptr.p;
-    DevArray<uint8_t> clean(n_h);
-    launch("pattern_reuse", row_clean_kernel, grid_for(n_h), dim3(kBlock), 0, n_h, rows_h, adj.offsets.p, adj.cells.p,
-           plan.cellsig.p, pc.sig.p, prev_indptr, V->bs, clean.p, counts.p, reuse_maxlen.p);
-    DevArray<int32_t> idx_d, idx_c;
-    n_d = compact("pattern_reuse", n_h, FlagIsZero{clean.p}, idx_d);
-    n_clean = n_h - n_d;
-    dirty_rows.alloc(n_d);
-    if (n_d > 0)
-      launch("pattern_reuse", gather_i32_kernel, grid_for(n_d), dim3(kBlock), 0, n_d, idx_d.p, rows_h, dirty_rows.p);
-    if (n_clean > 0)
-    {
-      (void)compact("pattern_reuse", n_h, FlagSet8{clean.p}, idx_c);
-      clean_rows.alloc(n_clean);
-      launch("pattern_reuse", gather_i32_kernel, grid_for(n_clean), dim3(kBlock), 0, n_clean, idx_c.p, rows_h, clean_rows.p);
-    }
-    rows_d = dirty_rows.p;
-    P->n_reused_rows = n_clean;
-    if (env_present<Sw::PLAN_DEBUG>())
-      fprintf(stderr, "cutfemx_amd: pattern reuse: %lld of %lld hashed rows copy their columns\n", (long long)n_clean, (long long)n_h);
+    tmp_short.alloc(n_short * 128);
+    tmp_long.alloc(n_long * 512);
   }
-  PatArgs S{};
-  S.n_active = use_stencil ? n_h_c.devn() : DevN(n_d); S.active_rows = rows_d;
+  S1.n_active = n_short; S1.active_rows = short_rows.p; S1.tmp = staged_sets ? tmp_short.p : nullptr;
+  S2.n_active = n_long; S2.active_rows = long_rows.p; S2.tmp = staged_sets ? tmp_long.p : nullptr; S2.len = len.p + n_short;
+  // rows_d = [the plan's special rows in plan order | other rows]: the position in rows_d is the facet-incidence index
+  if (rows_d == hashed.p && plan.nfacets.cap() > 0)
+  {
+    S1.row_pos = short_idx.p; S1.n_first = n_special_x;
+    if (n_long > 0) { S2.row_pos = long_idx.p; S2.n_first = n_special_x; }
+  }
+  if (n_short > 0) launch("pattern_rows_short", pattern_rows_kernel<16, 128>, wave_grid((n_short + 3) / 4), dim3(kWave), 0, S1);
+  if (n_long > 0) launch("pattern_rows_wide", pattern_rows_kernel<64, 512>, wave_grid(n_long), dim3(kWave), 0, S2);
+  if (read_scalar(overflow.p))
+  {
+    // a short static list with more than 127 - 40 facet couplings, or a row beyond 511: all rows wide from now on
+    V->lists_short_overflow = true;
+    V->long_rows = true; // (the 64-slot attempt below could only overflow again)
+    overflow.zero();
+    maxlen.zero();
+    return false;
+  }
+  write = staged_sets ? HashWrite::SplitStaged : HashWrite::SplitInPlace;
+  return true;
+}
+
+void PatternBuild::build_hash_sets()
+{
+  S.n_active = use_stencil ? plan.n_special_rows.devn() : DevN(n_d); S.active_rows = rows_d;
   S.nd = V->ndofs_cell; S.bs = V->bs; S.dofmap = V->dofmap.p;
   if (plan.any_cells)
   {
@@ -4184,110 +4267,56 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
     S.d2f_off = plan.d2f_offsets.p; S.d2f = plan.d2f.p; S.facet_rows = plan.facet_rows.p;
     S.special_mark = plan.special_mark.p; S.special_pos = plan.special_pos.p;
   }
-  DevArray<int32_t> len(n_d), tmp;
-  ZeroFlag overflow, maxlen;
+  len.alloc(n_d);
   // (the rows off the active set are never read from `counts`: indptr_*_kernel knows their length)
   S.len = len.p; S.counts = counts.p; S.overflow = overflow.p; S.maxlen = maxlen.p;
-  int T = 64;
-  // lists path: the hashed rows split by the length of their static list -- short rows (the edge dofs of a degree-2
-  // space: ~85 % of the rows) take 16 lanes and a 128-slot set, 4 rows per wavefront, the others one wavefront and
-  // 512 slots; both count first and build each set again to write it in place
-  constexpr int kShortLen = 40;
-  DevArray<int32_t> short_rows, long_rows, short_idx, long_idx, tmp_short, tmp_long;
-  bool staged_sets = false;
-  int64_t n_short = 0, n_long = 0;
-  bool split_hashed = false;
-  if (use_lists && n_d > 0 && !V->lists_short_overflow)
+  if (n_d == 0) return;
+  if (use_lists && !V->lists_short_overflow && hash_sets_short_long()) return;
+  // every hashed row alike: 64-slot sets four lanes per row, else 512 slots, else 2048, one wavefront per row
+  bool wide = V->long_rows;
+  write = HashWrite::Staged64;
+  if (!wide)
   {
-    n_short = compact("pattern_split", n_d, StaticLenTest{rows_d, st.offsets.p, kShortLen, false}, short_idx);
-    n_long = n_d - n_short;
-    short_rows.alloc(n_short);
-    long_rows.alloc(n_long);
-    if (n_short > 0)
-      launch("pattern_split", gather_i32_kernel, grid_for(n_short), dim3(kBlock), 0, n_short, short_idx.p, rows_d, short_rows.p);
-    if (n_long > 0)
-    {
-      compact("pattern_split", n_d, StaticLenTest{rows_d, st.offsets.p, kShortLen, true}, long_idx);
-      launch("pattern_split", gather_i32_kernel, grid_for(n_long), dim3(kBlock), 0, n_long, long_idx.p, rows_d, long_rows.p);
-    }
-    split_hashed = true;
-    T = 512;
-    PatArgs S1 = S, S2 = S;
-    // one pass: every set is ranked into a staging row (128 / 512 columns per row: 6 + 4.5 GB at BASELINE config 4),
-    // copied into the CSR arrays once the row offsets are known -- building each set a second time cost as much again
-    size_t free_b = 0, total_b = 0;
-    CFX_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t need = ((size_t)n_short * 128 + (size_t)n_long * 512) * sizeof(int32_t);
-    staged_sets = need < free_b / 2;
-    if (staged_sets)
-    {
-      tmp_short.alloc(n_short * 128);
-      tmp_long.alloc(n_long * 512);
-    }
-    S1.n_active = n_short; S1.active_rows = short_rows.p; S1.tmp = staged_sets ? tmp_short.p : nullptr;
-    S2.n_active = n_long; S2.active_rows = long_rows.p; S2.tmp = staged_sets ? tmp_long.p : nullptr; S2.len = len.p + n_short;
-    // rows_d = [the plan's special rows in plan order | other rows]: the position in rows_d is the facet-incidence index
-    if (rows_d == hashed.p && plan.nfacets.cap() > 0)
-    {
-      S1.row_pos = short_idx.p; S1.n_first = n_special_x;
-      if (n_long > 0) { S2.row_pos = long_idx.p; S2.n_first = n_special_x; }
-    }
-    if (n_short > 0) launch("pattern_rows_short", pattern_rows_kernel<16, 128>, wave_grid((n_short + 3) / 4), dim3(kWave), 0, S1);
-    if (n_long > 0) launch("pattern_rows_wide", pattern_rows_kernel<64, 512>, wave_grid(n_long), dim3(kWave), 0, S2);
-    if (read_scalar(overflow.p))
-    {
-      // a short static list with more than 127 - 40 facet couplings, or a row beyond 511: all rows wide from now on
-      V->lists_short_overflow = true;
-      V->long_rows = true; // (the 64-slot attempt below could only overflow again)
-      split_hashed = false;
-      overflow.zero();
-      maxlen.zero();
-    }
+    tmp.alloc(n_d * 64);
+    S.tmp = tmp.p;
+    launch("pattern_rows", pattern_rows_kernel<4, 64>, wave_grid((n_d + 15) / 16), dim3(kWave), 0, S);
+    // stencil path (P1): the overflow flag travels with the longest row and nnz in ONE read-back further down; an
+    // overflow (a row with more than 63 columns) then restarts the build on the wide path
+    if (use_stencil) deferred = true;
+    else wide = read_scalar(overflow.p) != 0;
   }
-  bool deferred = false;
-  if (n_d > 0 && !split_hashed)
+  if (!wide) return;
+  V->long_rows = true; // P2 / vector spaces: skip the narrow attempt next time (150 ms of 450 at config 4)
+  // long rows (P2, vector spaces, many facet couplings): one wavefront per row with a
+  // 512-slot set.  n_active * 512 staged columns would be ~150 GB for config 4, so the
+  // wide path counts first and builds each set again to write it in place.
+  write = HashWrite::Wide;
+  overflow.zero();
+  maxlen.zero();
+  tmp.release();
+  S.tmp = nullptr;
+  // (the stencil path may have come here with its row count still in HBM: the wide kernels take it exact; the
+  // other paths hash the list they were given -- n_d rows, exact already)
+  if (use_stencil) { S.n_active = DevN(plan.n_special_rows.value()); n_d = S.n_active.cap; }
+  else S.n_active = DevN(n_d);
+  if (!V->huge_rows) launch("pattern_rows_wide", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
+  if (V->huge_rows || read_scalar(overflow.p))
   {
-    bool wide = V->long_rows;
-    if (!wide)
-    {
-      tmp.alloc(n_d * 64);
-      S.tmp = tmp.p;
-      launch("pattern_rows", pattern_rows_kernel<4, 64>, wave_grid((n_d + 15) / 16), dim3(kWave), 0, S);
-      // stencil path (P1): the overflow flag travels with the longest row and nnz in ONE read-back further down; an
-      // overflow (a row with more than 63 columns) then restarts the build on the wide path
-      if (use_stencil) deferred = true;
-      else wide = read_scalar(overflow.p) != 0;
-    }
-    if (wide)
-    {
-      V->long_rows = true; // P2 / vector spaces: skip the narrow attempt next time (150 ms of 450 at config 4)
-      // long rows (P2, vector spaces, many facet couplings): one wavefront per row with a
-      // 512-slot set.  n_active * 512 staged columns would be ~150 GB for config 4, so the
-      // wide path counts first and builds each set again to write it in place.
-      T = 512;
-      overflow.zero();
-      maxlen.zero();
-      tmp.release();
-      S.tmp = nullptr;
-      // (the stencil path may have come here with its row count still in HBM: the wide kernels take it exact; the
-      // other paths hash the list they were given -- n_d rows, exact already)
-      if (use_stencil) { S.n_active = DevN(n_h_c.value()); n_d = S.n_active.cap; }
-      else S.n_active = DevN(n_d);
-      if (!V->huge_rows) launch("pattern_rows_wide", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
-      if (V->huge_rows || read_scalar(overflow.p))
-      {
-        // a row beyond 511 columns (a vertex of high valence in a degree-2 space, a hub of facet couplings): the same
-        // kernel with a 2048-slot set.  Such a pattern is assembled by the entity-parallel kernels (assemble_matrix_rows
-        // gathers rows of at most 512 columns).  The flag stays with the space: its later patterns start here.
-        V->huge_rows = true;
-        T = 2048;
-        overflow.zero();
-        maxlen.zero();
-        launch("pattern_rows_huge", pattern_rows_kernel<64, 2048>, wave_grid(n_d), dim3(kWave), 0, S);
-        require(!read_scalar(overflow.p), CFX_ERR_RUNTIME, "sparsity: a row couples more than 2047 dofs");
-      }
-    }
+    // a row beyond 511 columns (a vertex of high valence in a degree-2 space, a hub of facet couplings): the same
+    // kernel with a 2048-slot set.  Such a pattern is assembled by the entity-parallel kernels (assemble_matrix_rows
+    // gathers rows of at most 512 columns).  The flag stays with the space: its later patterns start here.
+    V->huge_rows = true;
+    write = HashWrite::Huge;
+    overflow.zero();
+    maxlen.zero();
+    launch("pattern_rows_huge", pattern_rows_kernel<64, 2048>, wave_grid(n_d), dim3(kWave), 0, S);
+    require(!read_scalar(overflow.p), CFX_ERR_RUNTIME, "sparsity: a row couples more than 2047 dofs");
   }
+}
+
+// False: a row of the stencil path went beyond 63 columns and the nested call has done the whole build again, wide
+bool PatternBuild::sum_row_offsets()
+{
   if (use_stencil)
   {
     // (the row lengths come out of the mask pass when the masks are built here; a plan whose masks exist already --
@@ -4299,63 +4328,67 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
   if (!deferred) P->max_row_len = plan.n_active_rows.cap() > 0 ? read_scalar(maxlen.p) : 1;
   if (any_full) P->max_row_len = std::max(P->max_row_len, st.max_len); // a copied row is at most the longest static list
   if (reuse && n_clean > 0) P->max_row_len = std::max(P->max_row_len, read_scalar(reuse_maxlen.p)); // ... or of the previous pattern
-  if (env_present<Sw::PLAN_DEBUG>()) fprintf(stderr, "cutfemx_amd: pattern max row length %d (static lists %d)\n", P->max_row_len, st.max_len);
+  if (env_present<Sw::PLAN_DEBUG>())
+    fprintf(stderr, "cutfemx_amd: pattern max row length %d (static lists %d)\n", P->max_row_len, st.max_len);
   P->indptr.alloc(P->nrows + 1);
+  const int64_t ntiles = (P->nrows + kTile - 1) / kTile;
+  DevArray<int64_t> sums(ntiles), offs(ntiles + 1);
+  ChainState chain{};
+  CountJobs after{};
+  if (deferred)
   {
-    const int64_t ntiles = (P->nrows + kTile - 1) / kTile;
-    DevArray<int64_t> sums(ntiles), offs(ntiles + 1);
-    ChainState chain{};
-    CountJobs after{};
-    if (deferred)
-    {
-      // overflow flag, longest row and nnz in one round trip -- or, inside a step, none: nnz stays in HBM, the flag
-      // has to repeat the last step's answer and the longest row its size class (what the host picks kernels by)
-      const char* names[3] = {"pattern.overflow", "pattern.max_row_len", "pattern.nnz"};
-      CountSource src[3];
-      src[0].src = overflow.p; src[0].kind = kCountI32; src[0].mode = kCountMustEqual;
-      src[1].src = maxlen.p; src[1].kind = kCountI32; src[1].mode = kCountSizeClass;
-      src[2].src = offs.p + ntiles; src[2].kind = kCountI64;
-      Count t[3];
-      CountPlan cp(3, names, src);
-      // (inside a step nnz's capacity is known before the rows are summed: reduce + offsets + write in one chained
-      // launch -- unless the recorded step found a long row: the host then leaves below, before any kernel that could
-      // publish)
-      chain = fused_chain(cp.publish && cp.counts[0].cap() == 0, ntiles);
-      if (chain.state) after = cp.take_jobs();
-      else
-      {
-        launch("pattern_indptr", indptr_reduce_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs,
-               plan.rowmark.p, counts.p, sums.p);
-        exclusive_scan(sums.p, offs.p, ntiles, &cp);
-      }
-      cp.finish(t);
-      if (t[0].cap() != 0)
-      {
-        V->long_rows = true; // rows beyond 63 columns: build again, wide
-        build_pattern(a, P);
-        return;
-      }
-      P->max_row_len = std::max((int)t[1].cap(), 1);
-      P->nnz = t[2];
-    }
+    // overflow flag, longest row and nnz in one round trip -- or, inside a step, none: nnz stays in HBM, the flag
+    // has to repeat the last step's answer and the longest row its size class (what the host picks kernels by)
+    const char* names[3] = {"pattern.overflow", "pattern.max_row_len", "pattern.nnz"};
+    CountSource src[3];
+    src[0].src = overflow.p; src[0].kind = kCountI32; src[0].mode = kCountMustEqual;
+    src[1].src = maxlen.p; src[1].kind = kCountI32; src[1].mode = kCountSizeClass;
+    src[2].src = offs.p + ntiles; src[2].kind = kCountI64;
+    Count t[3];
+    CountPlan cp(3, names, src);
+    // (inside a step nnz's capacity is known before the rows are summed: reduce + offsets + write in one chained
+    // launch -- unless the recorded step found a long row: the host then leaves below, before any kernel that could
+    // publish)
+    chain = fused_chain(cp.publish && cp.counts[0].cap() == 0, ntiles);
+    if (chain.state) after = cp.take_jobs();
     else
     {
-      launch("pattern_indptr", indptr_reduce_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs, plan.rowmark.p,
-             counts.p, sums.p);
-      exclusive_scan(sums.p, offs.p, ntiles);
-      P->nnz = Count(read_scalar(offs.p + ntiles));
+      launch("pattern_indptr", indptr_reduce_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs,
+             plan.rowmark.p, counts.p, sums.p);
+      exclusive_scan(sums.p, offs.p, ntiles, &cp);
     }
-    P->indices.alloc(P->nnz.cap());
-    // CFX_STAGING_NAN=1 (tests): the block cache hands a step the previous step's buffer, in which a row that nobody
-    // wrote could still hold the right columns -- every index starts as -1, before the first writer
-    if (env_is<Sw::STAGING_NAN>('1') && P->nnz.cap() > 0) dev_fill(P->indices.p, 0xff, sizeof(int32_t) * (size_t)P->nnz.cap());
-    if (chain.state)
-      launch("pattern_indptr", indptr_chained_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs,
-             plan.rowmark.p, counts.p, P->indptr.p, P->indices.p, P->nnz.cap(), chain, offs.p + ntiles, after);
-    else
-      launch("pattern_indptr", indptr_write_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs,
-             plan.rowmark.p, counts.p, offs.p, P->indptr.p, P->indices.p, P->nnz.devn());
+    cp.finish(t);
+    if (t[0].cap() != 0)
+    {
+      V->long_rows = true; // rows beyond 63 columns: build again, wide
+      build_pattern(a, P);
+      return false;
+    }
+    P->max_row_len = std::max((int)t[1].cap(), 1);
+    P->nnz = t[2];
   }
+  else
+  {
+    launch("pattern_indptr", indptr_reduce_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs, plan.rowmark.p,
+           counts.p, sums.p);
+    exclusive_scan(sums.p, offs.p, ntiles);
+    P->nnz = Count(read_scalar(offs.p + ntiles));
+  }
+  P->indices.alloc(P->nnz.cap());
+  // CFX_STAGING_NAN=1 (tests): the block cache hands a step the previous step's buffer, in which a row that nobody
+  // wrote could still hold the right columns -- every index starts as -1, before the first writer
+  if (env_is<Sw::STAGING_NAN>('1') && P->nnz.cap() > 0) dev_fill(P->indices.p, 0xff, sizeof(int32_t) * (size_t)P->nnz.cap());
+  if (chain.state)
+    launch("pattern_indptr", indptr_chained_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs,
+           plan.rowmark.p, counts.p, P->indptr.p, P->indices.p, P->nnz.cap(), chain, offs.p + ntiles, after);
+  else
+    launch("pattern_indptr", indptr_write_kernel, dim3((unsigned)ntiles), dim3(kBlock), 0, P->nrows, V->bs,
+           plan.rowmark.p, counts.p, offs.p, P->indptr.p, P->indices.p, P->nnz.devn());
+  return true;
+}
+
+void PatternBuild::write_columns()
+{
   if (use_stencil && space_stencil_tiles(V).tiles_usable && plan.n_plain_tiles.cap() > 0)
   {
     PatTileArgs T{};
@@ -4396,19 +4429,20 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
     launch("pattern_reuse", pattern_copy_prev_kernel<8>, grid_for(n_clean * 8), dim3(kBlock), 0, n_clean, clean_rows.p, V->bs,
            pc.live ? pc.live->indptr.p : pc.indptr.p, pc.live ? pc.live->indices.p : pc.indices.p, P->indptr.p, P->indices.p);
   }
-  if (any_full && V->bs == 1)
-    launch("pattern_plain_write", pattern_plain_copy_runs_kernel, wave_grid((n_plain_x + kWave - 1) / kWave), dim3(kWave), 0,
-           n_plain_x, plan.plain_rows.p, full.p, st.offsets.p, st.nbr.p, P->indptr.p, P->indices.p);
-  else if (any_full && V->bs == 3)
-    launch("pattern_plain_write", pattern_plain_copy_block_kernel<3>, wave_grid((n_plain_x + kWave - 1) / kWave), dim3(kWave), 0,
-           n_plain_x, plan.plain_rows.p, full.p, st.offsets.p, st.nbr.p, P->indptr.p, P->indices.p);
-  else if (any_full && V->bs == 2)
-    launch("pattern_plain_write", pattern_plain_copy_block_kernel<2>, wave_grid((n_plain_x + kWave - 1) / kWave), dim3(kWave), 0,
-           n_plain_x, plan.plain_rows.p, full.p, st.offsets.p, st.nbr.p, P->indptr.p, P->indices.p);
+  auto copy_lists = [&](auto kernel) // (one wavefront per 64 plain rows)
+  {
+    launch("pattern_plain_write", kernel, wave_grid((n_plain_x + kWave - 1) / kWave), dim3(kWave), 0, n_plain_x,
+           plan.plain_rows.p, full.p, st.offsets.p, st.nbr.p, P->indptr.p, P->indices.p);
+  };
+  if (any_full && V->bs == 1) copy_lists(pattern_plain_copy_runs_kernel);
+  else if (any_full && V->bs == 3) copy_lists(pattern_plain_copy_block_kernel<3>);
+  else if (any_full && V->bs == 2) copy_lists(pattern_plain_copy_block_kernel<2>);
   else if (any_full)
     launch("pattern_plain_write", pattern_plain_copy_kernel<8>, grid_for(n_plain_x * 8), dim3(kBlock), 0,
            n_plain_x, plan.plain_rows.p, full.p, st.offsets.p, st.nbr.p, V->bs, P->indptr.p, P->indices.p);
-  if (split_hashed && staged_sets)
+  const HashWrite how = n_d > 0 ? write : HashWrite::None;
+  S.indptr = P->indptr.p; S.indices = P->indices.p;
+  if (how == HashWrite::SplitStaged)
   {
     if (n_short > 0)
       launch("pattern_write", pattern_write_kernel<128>, grid_for(n_short * 8), dim3(kBlock), 0, n_short, short_rows.p, V->bs,
@@ -4417,44 +4451,51 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
       launch("pattern_write", pattern_write_kernel<512>, grid_for(n_long * 8), dim3(kBlock), 0, n_long, long_rows.p, V->bs,
              tmp_long.p, len.p + n_short, P->indptr.p, P->indices.p);
   }
-  else if (split_hashed)
+  else if (how == HashWrite::SplitInPlace)
   {
     PatArgs S1 = S, S2 = S;
-    S1.n_active = n_short; S1.active_rows = short_rows.p; S1.tmp = nullptr; S1.indptr = P->indptr.p; S1.indices = P->indices.p;
-    S2.n_active = n_long; S2.active_rows = long_rows.p; S2.tmp = nullptr; S2.indptr = P->indptr.p; S2.indices = P->indices.p;
+    S1.n_active = n_short; S1.active_rows = short_rows.p; S1.tmp = nullptr;
+    S2.n_active = n_long; S2.active_rows = long_rows.p; S2.tmp = nullptr;
     if (n_short > 0) launch("pattern_rows_short_write", pattern_rows_kernel<16, 128>, wave_grid((n_short + 3) / 4), dim3(kWave), 0, S1);
     if (n_long > 0) launch("pattern_rows_wide_write", pattern_rows_kernel<64, 512>, wave_grid(n_long), dim3(kWave), 0, S2);
   }
-  else if (n_d > 0)
+  else if (how == HashWrite::Staged64)
+    launch("pattern_write", pattern_write_kernel<64>, grid_for(n_d * 8), dim3(kBlock), 0, S.n_active, rows_d, V->bs, tmp.p,
+           len.p, P->indptr.p, P->indices.p);
+  else if (how == HashWrite::Wide)
+    launch("pattern_rows_wide_write", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
+  else if (how == HashWrite::Huge)
+    launch("pattern_rows_huge_write", pattern_rows_kernel<64, 2048>, wave_grid(n_d), dim3(kWave), 0, S);
+}
+
+// the plain rows that copied their static list, as the pattern's full_rows (they get gather kernels of their own)
+void PatternBuild::list_copied_rows()
+{
+  P->n_full_rows = select_rows("pattern_full_rows", n_plain_x, FlagSet8{full.p}, plan.plain_rows.p, P->full_rows);
+  P->full_plan = plan.serial;
+}
+
+// full_rows = [dofs with at most 32 neighbours | the others]: the edge dofs of a degree-2 space (7 of 8 dofs, at most
+// 27 neighbours on Kuhn meshes) need a third of the LDS accumulators of the vertex dofs (65) -- more dofs in flight
+void PatternBuild::split_full_rows()
+{
+  P->n_full_short = 0;
+  if (P->n_full_rows == 0) return;
+  DevArray<int32_t> idx_s, idx_l, sorted(P->n_full_rows);
+  const int64_t ns = compact("pattern_full_rows", P->n_full_rows, StaticLenTest{P->full_rows.p, st.offsets.p, 32, false}, idx_s);
+  if (ns > 0 && ns < P->n_full_rows)
   {
-    if (T == 64)
-      launch("pattern_write", pattern_write_kernel<64>, grid_for(n_d * 8), dim3(kBlock), 0, S.n_active, rows_d, V->bs, tmp.p,
-             len.p, P->indptr.p, P->indices.p);
-    else
-    {
-      S.indptr = P->indptr.p; S.indices = P->indices.p;
-      if (T == 2048) launch("pattern_rows_huge_write", pattern_rows_kernel<64, 2048>, wave_grid(n_d), dim3(kWave), 0, S);
-      else launch("pattern_rows_wide_write", pattern_rows_kernel<64, 512>, wave_grid(n_d), dim3(kWave), 0, S);
-    }
+    (void)compact("pattern_full_rows", P->n_full_rows, StaticLenTest{P->full_rows.p, st.offsets.p, 32, true}, idx_l);
+    launch("pattern_full_rows", gather_i32_kernel, grid_for(ns), dim3(kBlock), 0, ns, idx_s.p, P->full_rows.p, sorted.p);
+    launch("pattern_full_rows", gather_i32_kernel, grid_for(P->n_full_rows - ns), dim3(kBlock), 0, P->n_full_rows - ns,
+           idx_l.p, P->full_rows.p, sorted.p + ns);
+    P->full_rows = std::move(sorted);
   }
-  // full_rows = [dofs with at most 32 neighbours | the others]: the edge dofs of a degree-2 space (7 of 8 dofs, at most
-  // 27 neighbours on Kuhn meshes) need a third of the LDS accumulators of the vertex dofs (65) -- more dofs in flight
-  auto split_full_rows = [&]()
-  {
-    P->n_full_short = 0;
-    if (P->n_full_rows == 0) return;
-    DevArray<int32_t> idx_s, idx_l, sorted(P->n_full_rows);
-    const int64_t ns = compact("pattern_full_rows", P->n_full_rows, StaticLenTest{P->full_rows.p, st.offsets.p, 32, false}, idx_s);
-    if (ns > 0 && ns < P->n_full_rows)
-    {
-      (void)compact("pattern_full_rows", P->n_full_rows, StaticLenTest{P->full_rows.p, st.offsets.p, 32, true}, idx_l);
-      launch("pattern_full_rows", gather_i32_kernel, grid_for(ns), dim3(kBlock), 0, ns, idx_s.p, P->full_rows.p, sorted.p);
-      launch("pattern_full_rows", gather_i32_kernel, grid_for(P->n_full_rows - ns), dim3(kBlock), 0, P->n_full_rows - ns,
-             idx_l.p, P->full_rows.p, sorted.p + ns);
-      P->full_rows = std::move(sorted);
-    }
-    P->n_full_short = ns;
-  };
+  P->n_full_short = ns;
+}
+
+void PatternBuild::classify_gather_rows()
+{
   P->built_plan = plan.serial;
   P->stencil_plan = use_stencil ? plan.serial : 0;
   // spaces with long rows (degree 2): the gather assembly runs the short rows 8 lanes per row
@@ -4465,22 +4506,14 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
   {
     // vector-valued degree 2 with slot records and one uncut cell integral: the copied rows (dofs) take
     // assemble_rows_block_plain_kernel, the other active rows keep the searching block kernel
-    int n_std = 0;
-    for (const auto& I : a->integrals)
-      if (I.type == CFX_CELL && I.n_entities.cap() > 0) ++n_std;
-    if (n_std == 1 && space_stencil_slotn(V).slotn_ok)
+    if (uncut_cell_integrals(a).n == 1 && space_stencil_slotn(V).slotn_ok)
     {
-      DevArray<int32_t> pos;
-      P->n_full_rows = compact("pattern_full_rows", n_plain_x, FlagSet8{full.p}, pos);
-      P->full_rows.alloc(P->n_full_rows);
-      launch("pattern_full_rows", gather_i32_kernel, grid_for(P->n_full_rows), dim3(kBlock), 0, P->n_full_rows, pos.p,
-             plan.plain_rows.p, P->full_rows.p);
+      list_copied_rows();
       split_full_rows();
       P->n_rest_rows = n_h;
       P->rest_rows.alloc(n_h);
       if (n_h > 0)
         CFX_HIP(hipMemcpyAsync(P->rest_rows.p, rows_h, sizeof(int32_t) * (size_t)n_h, hipMemcpyDeviceToDevice, ctx().stream));
-      P->full_plan = plan.serial;
     }
   }
   if (P->max_row_len > 64 && V->bs == 1 && plan.n_active_rows.cap() > 0)
@@ -4491,22 +4524,10 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
     int64_t n_base = plan.n_active_rows.value();
     if (any_full && V->degree == 2)
     {
-      int n_std = 0;
-      bool closed = true;
-      for (const auto& I : a->integrals)
-        if (I.type == CFX_CELL && I.n_entities.cap() > 0)
-        {
-          ++n_std;
-          closed = closed && I.kernel == CFX_K_STIFFNESS && I.coefficient.n == 0;
-        }
-      if (n_std == 1 && closed && a->rank == 2 && env_on<Sw::P2_CLOSED>() && space_stencil_slotn(V).slotn_ok)
+      const UncutIntegrals uncut = uncut_cell_integrals(a);
+      if (uncut.n == 1 && uncut.closed && a->rank == 2 && env_on<Sw::P2_CLOSED>() && space_stencil_slotn(V).slotn_ok)
       {
-        DevArray<int32_t> pos;
-        P->n_full_rows = compact("pattern_full_rows", n_plain_x, FlagSet8{full.p}, pos);
-        P->full_rows.alloc(P->n_full_rows);
-        launch("pattern_full_rows", gather_i32_kernel, grid_for(P->n_full_rows), dim3(kBlock), 0, P->n_full_rows, pos.p,
-               plan.plain_rows.p, P->full_rows.p);
-        P->full_plan = plan.serial;
+        list_copied_rows();
         base_rows = rows_h;
         n_base = n_h;
         // rows_h = [interface rows | plain rows without a copied list]: the second part on its own
@@ -4534,6 +4555,20 @@ void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
               (long long)P->n_short_rows, (long long)P->n_mid_rows, (long long)P->n_long_rows);
     P->split_plan = plan.serial;
   }
+}
+
+} // namespace
+
+void build_pattern(cfx_form_s* a, cfx_pattern_s* P)
+{
+  if (a->rectangular()) { build_pattern_rectangular(a, P); return; }
+  PatternBuild B{a, P, a->V, row_plan(a), space_stencil(a->V)};
+  B.choose_hashed_rows();   // rows_h: the stencil path's special rows, [special | odd] of the lists path, or all active rows
+  B.split_reused_rows();    // rows_d / clean_rows: hashed now / copied from the space's previous pattern
+  B.build_hash_sets();      // lengths of the rows_d in `counts` and `len`; `write`: how their columns follow
+  if (!B.sum_row_offsets()) return; // plain-row lengths, longest row, indptr, room for the columns; or the restart, wide
+  B.write_columns();        // from plain masks, the previous pattern, static lists, staged sets, sets built again
+  B.classify_gather_rows(); // full / rest / odd rows, short / mid / long rows: what the gather assembly picks kernels by
   pattern_remember(a, P);
 }
 
