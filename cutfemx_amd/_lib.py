@@ -110,6 +110,16 @@ class ReinitInfoStruct(C.Structure):
 REINIT_CONVERGED, REINIT_MAX_ITER, REINIT_NO_INTERFACE = 1, 2, 3
 
 
+class ExtendOptions(C.Structure):
+    _fields_ = [("tol", C.c_double), ("inf_value", C.c_double), ("max_distance", C.c_double), ("max_iter", C.c_int32),
+                ("check_every", C.c_int32), ("normal_sign", C.c_double)]
+
+
+class ExtendInfoStruct(C.Structure):
+    _fields_ = [("reason", C.c_int32), ("sweeps", C.c_int32), ("seeds", C.c_int64), ("updates", C.c_int64),
+                ("transport_sweeps", C.c_int32), ("reserved", C.c_int32), ("transported", C.c_int64)]
+
+
 class PatternView(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("nnz", C.c_int64), ("indptr", C.c_void_p),
                 ("indices", C.c_void_p), ("ncols", C.c_int64)]
@@ -133,7 +143,7 @@ SYMBOLS = [
     "cfx_pattern_view_get", "cfx_pattern_reuse_stats", "cfx_pattern_destroy", "cfx_assemble_matrix", "cfx_assemble_matrix_zeroed", "cfx_assemble_vector", "cfx_assemble_scalar",
     "cfx_apply_lifting", "cfx_set_bc", "cfx_zero_rows", "cfx_csr_block_merge", "cfx_csr_permute", "cfx_tabulate_entity", "cfx_active_domain", "cfx_active_view", "cfx_deactivate_outside",
     "cfx_active_destroy", "cfx_csr_spmv", "cfx_cg_options_default", "cfx_cg_solve", "cfx_minres_options_default", "cfx_minres_solve",
-    "cfx_reinit_options_default", "cfx_reinitialize",
+    "cfx_reinit_options_default", "cfx_reinitialize", "cfx_extend_options_default", "cfx_extend_normal_velocity",
     "cfx_dist_unique_id", "cfx_dist_comm_create", "cfx_dist_comm_create_host", "cfx_dist_comm_create_device", "cfx_dist_comm_info", "cfx_dist_comm_destroy",
     "cfx_dist_scatter_forward", "cfx_dist_scatter_reverse_add", "cfx_dist_scatter_reverse_matrix", "cfx_dist_indicator_or",
     "cfx_dist_indicator_forward",

@@ -47,6 +47,7 @@
 // sweep launched on an empty list returns at once, so the result does not depend on how often the host looks
 // (check_every); with check_every = 0, a device phi and a device info the call makes no host round trip.
 #include "cfx_device.h"
+#include "cfx_reinit.h"
 #include "cfx_reinit_cell.h"
 
 using namespace cfx;
@@ -58,12 +59,6 @@ constexpr int kGroup = 8;        // lanes per target (24 tetrahedra / 6 triangle
 constexpr int kTargets = kBlock / kGroup;
 constexpr int kMaxGrid = 4096;   // blocks of the sweep kernels (the list length is on the device: they stride)
 
-struct ReinitRecord
-{
-  cfx_reinit_info info;        // what the caller receives (copied out as it stands)
-  unsigned long long count[2]; // sweep s walks list s & 1 of count[s & 1] targets and fills the other one
-};
-
 struct ReinitArgs
 {
   const double* x;       // [nv * 3]
@@ -73,7 +68,8 @@ struct ReinitArgs
   const int64_t* nbr_off; // the space's neighbour lists (the vertex itself included), or null: none
   const int32_t* nbr;
   int64_t nv, ncells;
-  double* phi;
+  const double* phi;
+  double* out;           // the signed result (phi itself for cfx_reinitialize)
   double* d;
   double* cand;          // by list position
   int32_t* list[2];
@@ -388,16 +384,17 @@ __global__ void __launch_bounds__(kBlock) reinit_finish_kernel(ReinitArgs A, int
   if (none || v >= A.nv) return;
   const double f = A.phi[v], dv = A.d[v];
   const double mag = A.band > 0.0 ? fmin(dv, A.band) : dv;
-  A.phi[v] = f >= 0.0 ? mag : -mag;
+  if (A.out) A.out[v] = f >= 0.0 ? mag : -mag;
 }
 
 template <int TDIM>
-void run(ReinitArgs A, const cfx_reinit_options& o, cfx_reinit_info* info)
+int sweeps(ReinitArgs A, const cfx_reinit_options& o, double* keep_near)
 {
   const dim3 gv = grid_for(A.nv, kBlock), gc = grid_for(A.ncells, kBlock);
   launch("reinit_begin", reinit_begin_kernel, gv, dim3(kBlock), 0, A);
   launch("reinit_seed", reinit_seed_kernel<TDIM>, gc, dim3(kBlock), 0, A);
   launch("reinit_start", reinit_start_kernel<TDIM>, gv, dim3(kBlock), 0, A);
+  if (keep_near) CFX_HIP(hipMemcpyAsync(keep_near, A.d, sizeof(double) * (size_t)A.nv, hipMemcpyDeviceToDevice, ctx().stream));
   const dim3 gs((unsigned)std::min<int64_t>((A.nv + kTargets - 1) / kTargets, kMaxGrid));
   const dim3 gm((unsigned)std::min<int64_t>((A.nv + kTargets - 1) / kTargets, kMaxGrid / 2)); // (one closing atomic per block)
   int launched = 0;
@@ -412,14 +409,75 @@ void run(ReinitArgs A, const cfx_reinit_options& o, cfx_reinit_info* info)
         read_scalar(&A.rec->count[launched & 1]) == 0ull)
       break;
   }
-  launch("reinit_finish", reinit_finish_kernel, gv, dim3(kBlock), 0, A, launched & 1);
-  if (!info) return;
-  if (is_device_pointer(info))
-    CFX_HIP(hipMemcpyAsync(info, &A.rec->info, sizeof(cfx_reinit_info), hipMemcpyDeviceToDevice, ctx().stream));
-  else
-    *info = read_scalar(&A.rec->info);
+  return launched & 1;
+}
+
+ReinitArgs arguments(cfx_space_t V, const DistanceStage& S, const double* phi, double* out)
+{
+  cfx_mesh_s* mesh = V->mesh;
+  const Adjacency& adj = V->dof_cells();
+  ReinitArgs A{};
+  A.x = mesh->x.p; A.conn = mesh->conn.p; A.voff = adj.offsets.p; A.vcells = adj.cells.p;
+  // (both mesh-static: built by the first call on the space, or by its first assembly)
+  const Stencil& st = space_stencil(V);
+  if (st.lists)
+  {
+    A.nbr_off = st.offsets.p;
+    A.nbr = st.nbr.p;
+  }
+  A.nv = mesh->nnodes; A.ncells = mesh->ncells;
+  A.phi = phi; A.out = out; A.d = S.d.p; A.cand = S.cand.p;
+  A.list[0] = S.list0.p; A.list[1] = S.list1.p;
+  A.bits = S.bits.p; A.rec = S.rec.p;
+  A.inf = S.inf;
+  A.band = S.band;
+  return A;
 }
 } // namespace
+
+namespace cfx
+{
+namespace reinit
+{
+void check_arguments(const char* who, cfx_space_t V, const cfx_reinit_options& o)
+{
+  const std::string w(who);
+  auto need = [&](bool ok, const char* what) { if (!ok) throw Error(CFX_ERR_INVALID_ARGUMENT, w + ": " + what); };
+  need(V->bs == 1, "the space must be scalar (block size 1)");
+  need(V->degree == 1, "the space must have degree 1");
+  need(V->dofmap.p == V->mesh->conn.p && V->ndofs == V->mesh->nnodes,
+       "the space must live on the geometry dofmap (created without a dofmap of its own)");
+  need(V->mesh->tdim == V->mesh->gdim && (V->mesh->tdim == 2 || V->mesh->tdim == 3), "triangles in 2-D or tetrahedra in 3-D");
+  need(o.tol >= 0.0, "tol is >= 0");
+  need(o.inf_value > 0.0, "inf_value is > 0");
+  need(o.max_iter >= 0 && o.check_every >= 0, "max_iter and check_every are >= 0");
+  need(o.max_iter <= 0x3fffffff, "max_iter too large");
+}
+
+void distance_stage(cfx_space_t V, const double* phi, const cfx_reinit_options& o, bool keep_near, DistanceStage& S)
+{
+  const int64_t nv = V->mesh->nnodes;
+  // workspace from the block cache: the distance, the candidates, two lists, the mark bits, the record
+  S.d.alloc(nv);
+  S.cand.alloc(nv);
+  S.list0.alloc(nv);
+  S.list1.alloc(nv);
+  S.bits.alloc((nv + 31) / 32);
+  S.rec.alloc(1);
+  if (keep_near) S.d0.alloc(nv);
+  S.inf = o.inf_value;
+  S.band = o.max_distance > 0.0 ? o.max_distance : 0.0;
+  const ReinitArgs A = arguments(V, S, phi, nullptr);
+  S.slot = V->mesh->tdim == 2 ? sweeps<2>(A, o, keep_near ? S.d0.p : nullptr) : sweeps<3>(A, o, keep_near ? S.d0.p : nullptr);
+}
+
+void write_signed_distance(cfx_space_t V, const DistanceStage& S, const double* phi, double* out)
+{
+  const ReinitArgs A = arguments(V, S, phi, out);
+  launch("reinit_finish", reinit_finish_kernel, grid_for(A.nv, kBlock), dim3(kBlock), 0, A, S.slot);
+}
+} // namespace reinit
+} // namespace cfx
 
 extern "C" {
 
@@ -444,46 +502,19 @@ int cfx_reinitialize(cfx_space_t V, double* phi, const cfx_reinit_options* opt, 
   else
     cfx_reinit_options_default(&o);
   require(V && phi, CFX_ERR_INVALID_ARGUMENT, "cfx_reinitialize: null space or phi");
-  require(V->bs == 1, CFX_ERR_INVALID_ARGUMENT, "cfx_reinitialize: the space must be scalar (block size 1)");
-  require(V->degree == 1, CFX_ERR_INVALID_ARGUMENT, "cfx_reinitialize: the space must have degree 1");
-  require(V->dofmap.p == V->mesh->conn.p && V->ndofs == V->mesh->nnodes, CFX_ERR_INVALID_ARGUMENT,
-          "cfx_reinitialize: the space must live on the geometry dofmap (created without a dofmap of its own)");
-  require(V->mesh->tdim == V->mesh->gdim && (V->mesh->tdim == 2 || V->mesh->tdim == 3), CFX_ERR_INVALID_ARGUMENT,
-          "cfx_reinitialize: triangles in 2-D or tetrahedra in 3-D");
-  require(o.tol >= 0.0, CFX_ERR_INVALID_ARGUMENT, "cfx_reinitialize: tol is >= 0");
-  require(o.inf_value > 0.0, CFX_ERR_INVALID_ARGUMENT, "cfx_reinitialize: inf_value is > 0");
-  require(o.max_iter >= 0 && o.check_every >= 0, CFX_ERR_INVALID_ARGUMENT, "cfx_reinitialize: max_iter and check_every are >= 0");
-  require(o.max_iter <= 0x3fffffff, CFX_ERR_INVALID_ARGUMENT, "cfx_reinitialize: max_iter too large");
+  check_arguments("cfx_reinitialize", V, o);
   ctx().ensure();
-  cfx_mesh_s* mesh = V->mesh;
-  const Adjacency& adj = V->dof_cells();
-  const int64_t nv = mesh->nnodes;
-  OutArray<double> po(phi, nv, true);
-  // workspace from the block cache: the distance, the candidates, two lists, the mark bits, the record
-  DevArray<double> d(nv), cand(nv);
-  DevArray<int32_t> list0(nv), list1(nv);
-  DevArray<unsigned> bits((nv + 31) / 32);
-  DevArray<ReinitRecord> rec(1);
-
-  ReinitArgs A{};
-  A.x = mesh->x.p; A.conn = mesh->conn.p; A.voff = adj.offsets.p; A.vcells = adj.cells.p;
-  // (both mesh-static: built by the first call on the space, or by its first assembly)
-  const Stencil& st = space_stencil(V);
-  if (st.lists)
+  OutArray<double> po(phi, V->mesh->nnodes, true);
+  DistanceStage S;
+  distance_stage(V, po.dev, o, false, S);
+  write_signed_distance(V, S, po.dev, po.dev);
+  if (info)
   {
-    A.nbr_off = st.offsets.p;
-    A.nbr = st.nbr.p;
+    if (is_device_pointer(info))
+      CFX_HIP(hipMemcpyAsync(info, &S.rec.p->info, sizeof(cfx_reinit_info), hipMemcpyDeviceToDevice, ctx().stream));
+    else
+      *info = read_scalar(&S.rec.p->info);
   }
-  A.nv = nv; A.ncells = mesh->ncells;
-  A.phi = po.dev; A.d = d.p; A.cand = cand.p;
-  A.list[0] = list0.p; A.list[1] = list1.p;
-  A.bits = bits.p; A.rec = rec.p;
-  A.inf = o.inf_value;
-  A.band = o.max_distance > 0.0 ? o.max_distance : 0.0;
-  if (mesh->tdim == 2)
-    run<2>(A, o, info);
-  else
-    run<3>(A, o, info);
   po.finish();
   CFX_API_END
 }

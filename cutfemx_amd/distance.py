@@ -54,6 +54,108 @@ def read_reinit_info(info_out) -> ReinitInfo:
     return ReinitInfo(int(st.reason), int(st.sweeps), int(st.seeds), int(st.updates))
 
 
+@dataclass
+class ExtendInfo(ReinitInfo):
+    """cfx_extend_info: the ReinitInfo of the distance stage, the transport sweeps that changed a payload and the
+    vertices that take their payload from sources (the others are near the interface, or were never reached)."""
+    transport_sweeps: int = 0
+    transported: int = 0
+
+
+@dataclass
+class NormalExtensionResult:
+    """What extend_normal_velocity returns (the reference's NormalExtensionResult): `speed` on V, `velocity` = speed x
+    unit normal on FunctionSpace(mesh, 1, bs=gdim), `signed_distance` on V, and the ExtendInfo (or the device buffer
+    given as info_out)."""
+    speed: Function
+    velocity: Function
+    signed_distance: Function
+    info: object = None
+
+
+def extend_info_buffer():
+    """A device buffer for `extend_normal_velocity(..., info_out=)`: 40 bytes that hold a cfx_extend_info; read with
+    read_extend_info."""
+    return _lib.DeviceBuffer(5, np.float64)
+
+
+def _extend_info(st) -> ExtendInfo:
+    return ExtendInfo(int(st.reason), int(st.sweeps), int(st.seeds), int(st.updates), int(st.transport_sweeps),
+                      int(st.transported))
+
+
+def read_extend_info(info_out) -> ExtendInfo:
+    """The ExtendInfo an extend_normal_velocity call left in `info_out` (one copy to the host)."""
+    raw = (info_out.numpy() if isinstance(info_out, _lib.DeviceBuffer) else info_out.cpu().numpy()).tobytes()
+    return _extend_info(_lib.ExtendInfoStruct.from_buffer_copy(raw[:C.sizeof(_lib.ExtendInfoStruct)]))
+
+
+def _count(a) -> int:
+    return int(a.numel()) if _lib.is_torch(a) else int(a.size)
+
+
+def extend_normal_velocity(phi: Function, interface_speed, *, normal_sign: float = 1.0, max_iter: int = 1000,
+                           tol: float = 1e-10, max_distance: float | None = None, check_every: int = 8, info_out=None):
+    """Carry a speed given on the zero contour of the P1 level set `phi` to the whole background mesh along the normals
+    (cutfemx.distance.extend_normal_velocity, python/cutfemx/distance.py:176-240), in HBM (cfx_extend_normal_velocity).
+
+    `interface_speed` is a Function on phi's space, or an array of one value per vertex: a P1 function w whose trace on
+    the zero contour is the speed (this engine has no interface mesh; a speed computed from a solution lives on the
+    background mesh anyway).  `phi` is not changed.  Returns a NormalExtensionResult: speed F (constant along the
+    normals of the distance field), velocity F n with n = normal_sign x the unit gradient of phi carried the same way,
+    and the signed distance -- bit for bit what `reinitialize` with the same `max_iter`, `tol`, `max_distance` and
+    `check_every` writes into a copy of phi.  numpy values give numpy results, device tensors device tensors.  Beyond
+    `max_distance` the speed and the velocity are 0.  Without an interface the results are zero-filled arrays that the
+    call did not touch, and info.reason is REINIT_NO_INTERFACE.  `info_out` (extend_info_buffer()): the info stays in
+    HBM; with device values and check_every = 0 the call makes no host round trip."""
+    V = phi.function_space
+    if V.degree != 1:
+        raise ValueError("extend_normal_velocity: the space of phi must have degree 1")
+    if V.bs != 1:
+        raise ValueError("extend_normal_velocity: the space of phi must be scalar (block size 1)")
+    nv, gdim = V.ndofs, V.mesh.gdim
+    w = interface_speed.values if isinstance(interface_speed, Function) else interface_speed
+    if isinstance(interface_speed, Function) and interface_speed.function_space is not V:
+        raise ValueError("extend_normal_velocity: interface_speed must live on the space of phi")
+    vals = phi.values
+    if _count(vals) != nv:
+        raise ValueError(f"extend_normal_velocity: phi.values must hold {nv} values")
+    if _count(w) != nv:
+        raise ValueError(f"extend_normal_velocity: interface_speed must hold {nv} values, one per vertex")
+    if info_out is not None and not _lib.is_device(info_out):
+        raise TypeError("extend_normal_velocity: info_out is a device buffer (extend_info_buffer())")
+    on_device = _lib.is_device(vals)
+    if on_device != _lib.is_device(w):
+        raise TypeError("extend_normal_velocity: phi.values and interface_speed must both be host or both be device arrays")
+    o = _lib.ExtendOptions()
+    _lib.check(_lib.load().cfx_extend_options_default(C.byref(o)))
+    o.max_iter, o.tol, o.check_every, o.normal_sign = int(max_iter), float(tol), int(check_every), float(normal_sign)
+    o.max_distance = 0.0 if max_distance is None else float(max_distance)
+    keep: list = []
+    if on_device and _lib.is_torch(vals):
+        import torch
+        make = lambda n: torch.zeros(n, dtype=torch.float64, device=vals.device)
+    elif on_device:
+        def make(n):
+            buf = _lib.DeviceBuffer(n, np.float64)
+            _lib.check(_lib.lib().cfx_device_memset(C.c_void_p(buf.ptr), 0, C.c_size_t(8 * n)))
+            return buf
+    else:
+        make = lambda n: np.zeros(n, dtype=np.float64)
+    speed, velocity, dist = make(nv), make(nv * gdim), make(nv)
+    ptr = lambda a: _lib.as_ptr(a, np.float64, keep)
+    fn = _lib.lib().cfx_extend_normal_velocity
+    st = None if info_out is not None else _lib.ExtendInfoStruct()
+    info_ptr = ptr(info_out) if info_out is not None else C.byref(st)
+    _lib.check(fn(V._h, ptr(vals), ptr(w), ptr(speed), ptr(velocity), ptr(dist), C.byref(o), info_ptr))
+    from .mesh import FunctionSpace
+    if getattr(V, "_vector_space", None) is None:
+        V._vector_space = FunctionSpace(V.mesh, 1, bs=gdim)
+    return NormalExtensionResult(Function(V, values=speed, name="speed"), Function(V._vector_space, values=velocity, name="velocity"),
+                                 Function(V, values=dist, name="signed_distance"),
+                                 info_out if info_out is not None else _extend_info(st))
+
+
 def reinitialize(phi: Function, max_iter: int = 1000, tol: float = 1e-10, *, max_distance: float | None = None,
                  check_every: int = 8, info_out=None):
     """Turn the P1 level set `phi` into the signed distance to its own zero contour, in place on `phi.values` (a numpy

@@ -806,6 +806,63 @@ int cfx_reinit_options_default(cfx_reinit_options* opt); /* tol 1e-10, inf_value
 int cfx_reinitialize(cfx_space_t V, double* phi /* host or device, in place */,
                      const cfx_reinit_options* opt /* or NULL: the defaults */, cfx_reinit_info* info /* host or device, or NULL */);
 
+/* ---- normal extension: an interface speed carried to the background mesh along the normals, in HBM ------------------
+ * cutfemx.distance.extend_normal_velocity of the reference (python/cutfemx/distance.py:176-240,
+ * cpp/cutfemx/distance/normal_extension.h:321-485, which transports with fast_iterative.h:55-143): the stage of a
+ * moving-domain loop between "a normal speed on the interface" and "move phi".  V as for cfx_reinitialize (scalar, degree
+ * 1, geometry dofmap, triangles or tetrahedra); phi [nv] is read only and never changed.  interface_speed [nv] is a P1
+ * function w on the background mesh whose trace on the zero contour is the speed.  Outputs, each host or device, each may
+ * be NULL (skipped): speed [nv], velocity [nv * gdim] (blocked: the gdim components of a vertex in a row),
+ * signed_distance [nv].
+ * Deviations from the reference, on purpose: (1) the speed is given on V, not on an interface mesh -- this engine has no
+ * cut mesh object, and a speed computed from a solution on V lives there anyway; (2) the reference copies the payload of
+ * the best source at the moment a distance improves (normal_extension.h:388-452), so its result depends on the order of
+ * the updates; here the payload is a pure function of the final distance; (3) its near field is a loop of every near
+ * vertex over every interface element (normal_extension.h:337-380); here it is the reinitialisation's own; (4) no k_ring
+ * and no target_space: interpolating to another degree is the caller's.
+ *   1 distance     d is the d of cfx_reinitialize on the same phi, tol, inf_value, max_distance, max_iter, check_every;
+ *                  signed_distance = s_v min(d_v, B), bit-identical to what cfx_reinitialize writes into a copy of phi
+ *   2 near         a vertex is near when its final d_v equals its near-field value d0_v bit for bit (the iteration lowers
+ *                  values strictly: "never improved").  Of the seed cells K around v with dist(x_v, G_K) <= (1 + 1e-12)
+ *                  d0_v the one with the lowest cell index is taken; c the closest point of its piece G_K;
+ *                  F_v = (P1 interpolant of w in K)(c), n_v = normal_sign grad(phi)|_K / |grad(phi)|_K.
+ *                  phi_v == 0: F_v = w_v; the normal of the lowest-index incident seed cell, else of the lowest-index
+ *                  incident cell with a non-zero gradient, else 0
+ *   3 transported  every other reached vertex t: U(t, K) on the FINAL d over the incident cells and their sub-faces as
+ *                  the update forms it (single sources, pairs, the triple).  Candidates: U <= (1 + 1e-12) d_t; the lowest
+ *                  cell index, then the first sub-face in that order; none in the window: the least U, same tie order.
+ *                  With lambda the weights of the minimiser on that sub-face, the sources with d_s >= d_t or lambda_s <= 0
+ *                  are dropped and the rest renormalised to sum 1; F_t = sum lambda_s F_s, n_t = m / |m| with
+ *                  m = sum lambda_s n_s (|m| = 0: the normal of the source with the largest weight).  No source left: the
+ *                  payload of a vertex never reached.  Every kept source has d_s < d_t, so the dependencies have no
+ *                  cycle: the payload is unique and Jacobi sweeps reach it in at most as many sweeps as there are levels
+ *   4 output       speed = F, velocity = F n; a vertex never reached, or with d_v > B under a band, has F = 0, n = 0 and
+ *                  the clamped distance
+ * reason: CFX_REINIT_NO_INTERFACE (no output is written), CFX_REINIT_MAX_ITER (the distance or the transport had work
+ * left after max_iter sweeps each; the outputs are written), else CFX_REINIT_CONVERGED.  info: the fields of
+ * cfx_reinit_info, transport_sweeps (sweeps that changed a payload) and transported (vertices with a source record).
+ * Two calls give the same bits, and the result does not depend on check_every; check_every = 0 with device arrays and
+ * a device (or NULL) info makes no host round trip. */
+typedef struct
+{
+  double tol, inf_value, max_distance /* <= 0: none */;
+  int32_t max_iter, check_every;
+  double normal_sign; /* 1.0: n points where phi grows */
+} cfx_extend_options;
+typedef struct
+{
+  int32_t reason, sweeps;
+  int64_t seeds, updates;
+  int32_t transport_sweeps, reserved;
+  int64_t transported;
+} cfx_extend_info;
+int cfx_extend_options_default(cfx_extend_options* opt); /* those of cfx_reinit_options_default, normal_sign 1.0; works
+                                                            without a GPU */
+int cfx_extend_normal_velocity(cfx_space_t V, const double* phi, const double* interface_speed, double* speed,
+                               double* velocity, double* signed_distance,
+                               const cfx_extend_options* opt /* or NULL: the defaults */,
+                               cfx_extend_info* info /* host or device, or NULL */);
+
 /* ---- float32 instantiation of the boundary --------------------------------------------------------------
  * python/cutfemx/wrappers/fem.cpp:490-500 declares the runtime assembly for <T, U> in {float, double}^2 and
  * wrappers/cut.cpp:403-407 the cut API for float and double: T = scalar type of MatrixCSR / Vector / Function,

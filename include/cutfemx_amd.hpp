@@ -870,5 +870,49 @@ inline void reinitialize(const fem::FunctionSpace& V, double* phi, const cfx_rei
 {
   check(cfx_reinitialize(V.handle.h, phi, &options, device_info));
 }
+
+/// cfx_extend_options with the library's defaults (those of ReinitOptions, normal_sign 1.0)
+struct ExtendOptions : cfx_extend_options
+{
+  ExtendOptions() { check(cfx_extend_options_default(this)); }
+};
+
+/// What extend_normal_velocity returns on host arrays (the reference's NormalExtensionResult): the speed [nv], the
+/// velocity [nv * gdim] (blocked) and the signed distance [nv], with the call's info.
+struct NormalExtensionResult
+{
+  std::vector<double> speed, velocity, signed_distance;
+  cfx_extend_info info{};
+};
+
+/// cutfemx::distance::extend_normal_velocity (cpp/cutfemx/distance/normal_extension.h:321-485): a speed on the zero
+/// contour of the P1 level set `phi` on `V` -- scalar, degree 1, on the geometry dofmap -- carried to every vertex along
+/// the normals, in HBM (cfx_extend_normal_velocity).  `interface_speed` holds one value per vertex: a P1 function on the
+/// background mesh whose trace on the contour is the speed (the reference takes it on an interface mesh; this engine has
+/// none).  `phi` is not changed.  Every reason is returned in the info; only bad arguments throw.
+inline NormalExtensionResult extend_normal_velocity(const fem::FunctionSpace& V, std::span<const double> phi,
+                                                    std::span<const double> interface_speed,
+                                                    const cfx_extend_options& options = ExtendOptions())
+{
+  const std::int64_t nv = V.ndofs;
+  if (V.bs != 1 || (std::int64_t)phi.size() != nv || (std::int64_t)interface_speed.size() != nv)
+    throw std::invalid_argument("extend_normal_velocity: one value of phi and of interface_speed per vertex of a scalar space");
+  const int gdim = V.ndofs_cell - 1; // (a P1 space of simplices with gdim = tdim: the library checks the rest)
+  NormalExtensionResult r;
+  r.speed.assign(static_cast<std::size_t>(nv), 0.0);
+  r.velocity.assign(static_cast<std::size_t>(nv * gdim), 0.0);
+  r.signed_distance.assign(static_cast<std::size_t>(nv), 0.0);
+  check(cfx_extend_normal_velocity(V.handle.h, phi.data(), interface_speed.data(), r.speed.data(), r.velocity.data(),
+                                   r.signed_distance.data(), &options, &r.info));
+  return r;
+}
+/// ... with raw pointers (host or device; an output may be nullptr and is then skipped) and the cfx_extend_info left in
+/// HBM (`device_info`, or nullptr): with device arrays and options.check_every = 0 the call makes no host round trip
+inline void extend_normal_velocity(const fem::FunctionSpace& V, const double* phi, const double* interface_speed, double* speed,
+                                   double* velocity, double* signed_distance, const cfx_extend_options& options,
+                                   cfx_extend_info* device_info)
+{
+  check(cfx_extend_normal_velocity(V.handle.h, phi, interface_speed, speed, velocity, signed_distance, &options, device_info));
+}
 } // namespace distance
 } // namespace cutfemx_amd
