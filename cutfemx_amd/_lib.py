@@ -120,6 +120,16 @@ class ExtendInfoStruct(C.Structure):
                 ("transport_sweeps", C.c_int32), ("reserved", C.c_int32), ("transported", C.c_int64)]
 
 
+class AdvectOptions(C.Structure):
+    _fields_ = [("dt", C.c_double), ("max_distance", C.c_double), ("inside_tol", C.c_double), ("order", C.c_int32),
+                ("max_steps", C.c_int32)]
+
+
+class AdvectInfoStruct(C.Structure):
+    _fields_ = [("located", C.c_int64), ("outside", C.c_int64), ("capped", C.c_int64), ("skipped", C.c_int64),
+                ("steps", C.c_int64), ("max_walk", C.c_int32), ("reserved", C.c_int32)]
+
+
 class PatternView(C.Structure):
     _fields_ = [("nrows", C.c_int64), ("nnz", C.c_int64), ("indptr", C.c_void_p),
                 ("indices", C.c_void_p), ("ncols", C.c_int64)]
@@ -144,6 +154,7 @@ SYMBOLS = [
     "cfx_apply_lifting", "cfx_set_bc", "cfx_zero_rows", "cfx_csr_block_merge", "cfx_csr_permute", "cfx_tabulate_entity", "cfx_active_domain", "cfx_active_view", "cfx_deactivate_outside",
     "cfx_active_destroy", "cfx_csr_spmv", "cfx_cg_options_default", "cfx_cg_solve", "cfx_minres_options_default", "cfx_minres_solve",
     "cfx_reinit_options_default", "cfx_reinitialize", "cfx_extend_options_default", "cfx_extend_normal_velocity",
+    "cfx_advect_options_default", "cfx_advect_level_set", "cfx_mesh_cell_neighbours",
     "cfx_dist_unique_id", "cfx_dist_comm_create", "cfx_dist_comm_create_host", "cfx_dist_comm_create_device", "cfx_dist_comm_info", "cfx_dist_comm_destroy",
     "cfx_dist_scatter_forward", "cfx_dist_scatter_reverse_add", "cfx_dist_scatter_reverse_matrix", "cfx_dist_indicator_or",
     "cfx_dist_indicator_forward",

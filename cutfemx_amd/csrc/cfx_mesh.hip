@@ -243,6 +243,15 @@ int cfx_mesh_info(cfx_mesh_t m, int* tdim, int* gdim, int64_t* nnodes, int64_t* 
   CFX_API_END
 }
 
+int cfx_mesh_cell_neighbours(cfx_mesh_t m, const int32_t** device_ptr)
+{
+  CFX_API_BEGIN
+  require(m != nullptr && device_ptr != nullptr, CFX_ERR_INVALID_ARGUMENT, "cfx_mesh_cell_neighbours: null argument");
+  ctx().ensure();
+  *device_ptr = m->cell_neighbours().p;
+  CFX_API_END
+}
+
 int cfx_mesh_destroy(cfx_mesh_t m)
 {
   CFX_API_BEGIN

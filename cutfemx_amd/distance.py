@@ -1,5 +1,7 @@
 """cutfemx.distance of the reference, the part a moving-domain loop needs: reinitialize(phi, max_iter, tol)
-(python/cutfemx/distance.py:154-160) -- a P1 level set back to a signed distance function, in HBM (cfx_reinitialize).
+(python/cutfemx/distance.py:154-160) -- a P1 level set back to a signed distance function, in HBM (cfx_reinitialize) --
+extend_normal_velocity (cfx_extend_normal_velocity), and advect, the demos' characteristic step that moves phi
+(cfx_advect_level_set).
 """
 from __future__ import annotations
 
@@ -154,6 +156,113 @@ def extend_normal_velocity(phi: Function, interface_speed, *, normal_sign: float
     return NormalExtensionResult(Function(V, values=speed, name="speed"), Function(V._vector_space, values=velocity, name="velocity"),
                                  Function(V, values=dist, name="signed_distance"),
                                  info_out if info_out is not None else _extend_info(st))
+
+
+@dataclass
+class AdvectInfo:
+    """cfx_advect_info: the vertices whose departure point was found in a cell (fixed dofs included), those whose walk
+    left the mesh, those that hit the step limit or had a non-finite target (unchanged), those beyond the band
+    (unchanged); the facet crossings of all walks and the most crossings of one vertex."""
+    located: int
+    outside: int
+    capped: int
+    skipped: int
+    steps: int
+    max_walk: int
+
+
+def advect_info_buffer():
+    """A device buffer for `advect(..., info_out=)`: 48 bytes that hold a cfx_advect_info; read with read_advect_info."""
+    return _lib.DeviceBuffer(6, np.float64)
+
+
+def _advect_info(st) -> AdvectInfo:
+    return AdvectInfo(int(st.located), int(st.outside), int(st.capped), int(st.skipped), int(st.steps), int(st.max_walk))
+
+
+def read_advect_info(info_out) -> AdvectInfo:
+    """The AdvectInfo an advect call left in `info_out` (one copy to the host)."""
+    raw = (info_out.numpy() if isinstance(info_out, _lib.DeviceBuffer) else info_out.cpu().numpy()).tobytes()
+    return _advect_info(_lib.AdvectInfoStruct.from_buffer_copy(raw[:C.sizeof(_lib.AdvectInfoStruct)]))
+
+
+def advect(phi: Function, velocity, dt: float, *, order: int = 2, max_distance: float | None = None, max_steps: int = 4096,
+           cells_out=None, info_out=None):
+    """Move the P1 level set `phi` along `velocity` over the time `dt` by semi-Lagrangian characteristics, in place on
+    `phi.values`, in HBM (cfx_advect_level_set; _advect_level_set_characteristics of the reference's
+    demo_compliance_optimization.py).  Returns an AdvectInfo.
+
+    `phi` lives on a scalar degree-1 space on the geometry dofmap.  `velocity` is a Function on a degree-1 space with
+    bs = gdim on the same mesh -- the `velocity` of a NormalExtensionResult goes in as it stands -- or an array of
+    nv * gdim values, the gdim components of a vertex in a row.  Every vertex takes the old phi at its departure point
+    x - dt v_mid (`order` 2: v_mid the velocity at x - dt/2 v; `order` 1: its own velocity), found by a walk through the
+    cells; a point outside the mesh takes the P1 extension of the boundary cell the walk left through.  `max_distance`
+    = B: vertices with |phi| > B keep their value -- the caller owes dt max|velocity| < B (reinitialize clamps to
+    exactly its band: a B a hair below that one skips the clamped vertices).  `max_steps`: a walk of more
+    crossings leaves its vertex unchanged and counts it as capped.  `cells_out`: an int32 array of nv entries that
+    receives the final cell of every vertex (-1: skipped or capped).  numpy values stay numpy, device tensors stay in
+    HBM; mixing the two raises TypeError.  `info_out` (advect_info_buffer()): the info stays in HBM and is returned as it
+    stands; with device arrays the call then makes no host round trip."""
+    V = phi.function_space
+    if V.degree != 1:
+        raise ValueError("advect: the space of phi must have degree 1")
+    if V.bs != 1:
+        raise ValueError("advect: the space of phi must be scalar (block size 1)")
+    nv, gdim = V.ndofs, V.mesh.gdim
+    if isinstance(velocity, Function):
+        W = velocity.function_space
+        if W.mesh is not V.mesh or W.degree != 1 or W.bs != gdim:
+            raise ValueError("advect: velocity must live on a degree-1 space with bs = gdim on the mesh of phi")
+        vel = velocity.values
+    else:
+        vel = velocity
+    vals = phi.values
+    on_device = _lib.is_device(vals)
+    if on_device != _lib.is_device(vel) or (cells_out is not None and on_device != _lib.is_device(cells_out)):
+        raise TypeError("advect: phi.values, velocity and cells_out must all be host or all be device arrays")
+    if info_out is not None and not _lib.is_device(info_out):
+        raise TypeError("advect: info_out is a device buffer (advect_info_buffer())")
+    keep: list = []
+    if on_device:
+        if _lib.is_torch(vals):
+            import torch
+            if vals.dtype != torch.float64 or not vals.is_contiguous():
+                raise TypeError("phi.values must be a contiguous float64 tensor (it is overwritten in place)")
+        pp = _lib.as_ptr(vals, np.float64, keep)
+    else:
+        if not (isinstance(vals, np.ndarray) and vals.dtype == np.float64 and vals.flags.c_contiguous):
+            vals = phi.values = np.ascontiguousarray(vals, dtype=np.float64)
+        pp = vals.ctypes.data_as(C.c_void_p)
+    if _count(vals) != nv:
+        raise ValueError(f"advect: phi.values must hold {nv} values")
+    if _count(vel) != nv * gdim:
+        raise ValueError(f"advect: velocity must hold {nv * gdim} values, {gdim} per vertex")
+    cp = None
+    if cells_out is not None:
+        if _count(cells_out) != nv:
+            raise ValueError(f"advect: cells_out must hold {nv} entries")
+        if _lib.is_torch(cells_out):
+            import torch
+            ok = cells_out.dtype == torch.int32 and cells_out.is_contiguous()
+        elif isinstance(cells_out, _lib.DeviceBuffer):
+            ok = cells_out.dtype == np.dtype(np.int32)
+        else:
+            ok = isinstance(cells_out, np.ndarray) and cells_out.dtype == np.int32 and cells_out.flags.c_contiguous
+        if not ok:
+            raise TypeError("advect: cells_out must be a contiguous int32 array (it is written in place)")
+        cp = _lib.as_ptr(cells_out, np.int32, keep)
+    o = _lib.AdvectOptions()
+    _lib.check(_lib.load().cfx_advect_options_default(C.byref(o)))
+    o.dt, o.order, o.max_steps = float(dt), int(order), int(max_steps)
+    o.max_distance = 0.0 if max_distance is None else float(max_distance)
+    fn = _lib.lib().cfx_advect_level_set
+    vp = _lib.as_ptr(vel, np.float64, keep)
+    if info_out is not None:
+        _lib.check(fn(V._h, pp, vp, pp, cp, C.byref(o), _lib.as_ptr(info_out, np.float64, keep)))
+        return info_out
+    st = _lib.AdvectInfoStruct()
+    _lib.check(fn(V._h, pp, vp, pp, cp, C.byref(o), C.byref(st)))
+    return _advect_info(st)
 
 
 def reinitialize(phi: Function, max_iter: int = 1000, tol: float = 1e-10, *, max_distance: float | None = None,

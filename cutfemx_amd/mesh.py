@@ -114,6 +114,14 @@ class Mesh:
     def conn(self) -> np.ndarray:
         return _lib.download(self.conn_ptr, self.num_cells * (self.tdim + 1), np.int32).reshape(-1, self.tdim + 1)
 
+    def cell_neighbours(self) -> np.ndarray:
+        """The mesh-static cell -> cell table (cfx_mesh_cell_neighbours), copied to the host: int32 [ncells, tdim + 1],
+        entry i of a row the cell across the facet opposite local vertex i, -1 on the boundary.  Built in HBM on first
+        use."""
+        p = C.c_void_p()
+        _lib.check(_lib.lib().cfx_mesh_cell_neighbours(self._h, C.byref(p)))
+        return _lib.download(p.value, self.num_cells * (self.tdim + 1), np.int32).reshape(-1, self.tdim + 1)
+
     def __del__(self):
         try:
             if self._h:

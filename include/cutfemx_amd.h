@@ -267,6 +267,11 @@ int cfx_mesh_create_box(int tdim, int n, cfx_mesh_t* out);
 int cfx_mesh_create_slab(int n, int z0, int nz, cfx_mesh_t* out);
 int cfx_mesh_info(cfx_mesh_t m, int* tdim, int* gdim, int64_t* nnodes, int64_t* ncells,
                   const double** x, const int32_t** conn);
+/* the mesh-static cell -> cell table in HBM, read only: int32 [ncells][tdim + 1], entry i of a row the cell across the
+ * facet opposite local vertex i, or -1 on the boundary.  Built on the device by the first call that needs it (this one,
+ * a ghost-penalty facet search, cfx_advect_level_set) from the vertex -> cells incidence; 16 B per tetrahedron, listed
+ * under cell_neighbours in cfx_space_static_bytes.  The pointer stays valid while the mesh lives. */
+int cfx_mesh_cell_neighbours(cfx_mesh_t m, const int32_t** device_ptr);
 int cfx_mesh_destroy(cfx_mesh_t m);
 
 /* ---- cut: cutfemx::cut / update / locate_entities / runtime_quadrature,
@@ -862,6 +867,57 @@ int cfx_extend_normal_velocity(cfx_space_t V, const double* phi, const double* i
                                double* velocity, double* signed_distance,
                                const cfx_extend_options* opt /* or NULL: the defaults */,
                                cfx_extend_info* info /* host or device, or NULL */);
+
+/* ---- advection: a P1 level set moved along a P1 velocity by semi-Lagrangian characteristics, in HBM ---------------------
+ * _advect_level_set_characteristics of the reference's demo (python/demo/demo_compliance_optimization.py:2071-2095:
+ * midpoint rule, bounding-box tree, compute_colliding_cells, Function.eval, all on the host): the stage of a
+ * moving-domain loop between cfx_extend_normal_velocity and cfx_reinitialize.  V as for cfx_reinitialize (scalar, degree 1,
+ * geometry dofmap, triangles in 2-D or tetrahedra in 3-D).  phi [nv] and velocity [nv * gdim] (blocked: the layout of
+ * cfx_extend_normal_velocity's velocity) are read, out [nv] is written; out may be phi itself (the result then goes
+ * through a workspace: every vertex reads other vertices' OLD values).  cells [nv] int32, or NULL.  Every array is host or
+ * device on its own, decided as in cfx_reinitialize.  For every vertex v at x_v:
+ *   1 skipped    max_distance = B > 0 and |phi_v| > B: out_v = phi_v.  THE CALLER OWES dt max|velocity| < B: a vertex
+ *                beyond the band is assumed to stay beyond the zero contour's reach, its old value is its new one.
+ *                cfx_reinitialize clamps to exactly ITS band, so a band a hair below that one skips the clamped vertices
+ *   2 departure  order 2 (default, the demo's rule): x_half = x_v - dt/2 velocity_v, v_mid = (P1 interpolant of
+ *                velocity)(x_half), x_dep = x_v - dt v_mid.  x_half == x_v bit for bit: v_mid = velocity_v, no walk.
+ *                order 1: x_dep = x_v - dt velocity_v.
+ *                x_dep == x_v bit for bit: out_v = phi_v exactly, v counts as located with a walk of 0 and
+ *                cells[v] = the lowest-numbered cell around v -- a vertex with zero velocity is a fixed dof
+ *   3 location   a visibility walk from the lowest-numbered cell incident to v.  In the current cell the barycentric
+ *                coordinates lambda of the target (Cramer's rule on the edge matrix, lambda_0 = 1 - the others); every
+ *                lambda_i >= -inside_tol: found.  Otherwise the facet opposite the most negative lambda is crossed, the
+ *                lowest local index on ties.  For order 2 the walk to x_dep goes on from the cell where the one to
+ *                x_half ended.  A boundary facet ends the walk in that cell: v is counted outside (what happened to the
+ *                walk to x_half does not count).  When one more crossing would exceed max_steps -- the two walks of
+ *                order 2 counted together -- or a coordinate of a target is not finite, v is counted capped, out_v = phi_v
+ *                and cells[v] = -1.  A NaN is never inside and never chooses a facet, so a walk through NaNs ends at the
+ *                step limit.  A vertex of no cell counts as outside with out_v = phi_v, cells[v] = -1
+ *   4 value      out_v = sum lambda_i phi_(K_i) in the final cell K with the unclamped lambda: for an outside vertex the P1
+ *                extension of the boundary cell the walk left through (the reference's closest-cell fallback followed by
+ *                eval); a linear phi stays linear up to the boundary.  The same rule gives v_mid when x_half is outside
+ *   5 cells      the final cell of v; -1 for skipped and capped vertices
+ *   6 info       located + outside + capped + skipped = nv; steps = the facet crossings of all walks, max_walk = the most
+ *                crossings of one vertex.  Host, device or NULL as for cfx_reinit_info
+ * Each vertex is one lane that reads only old arrays: two calls give the same bits, whatever the arrays' homes.  Every
+ * operation is homogeneous: coordinates, phi and dt x velocity scaled by a power of two give the scaled bits.  With
+ * device arrays and a device (or NULL) info the call makes no host round trip (cfx_sync_count does not grow) once the
+ * mesh's static tables exist. */
+typedef struct
+{
+  double dt, max_distance /* <= 0: none */, inside_tol;
+  int32_t order, max_steps;
+} cfx_advect_options;
+typedef struct
+{
+  int64_t located, outside, capped, skipped, steps;
+  int32_t max_walk, reserved;
+} cfx_advect_info;
+int cfx_advect_options_default(cfx_advect_options* opt); /* dt 0, max_distance 0, inside_tol 1e-12, order 2, max_steps 4096;
+                                                            works without a GPU */
+int cfx_advect_level_set(cfx_space_t V, const double* phi, const double* velocity, double* out /* may be phi */,
+                         int32_t* cells /* or NULL */, const cfx_advect_options* opt /* or NULL: the defaults */,
+                         cfx_advect_info* info /* host or device, or NULL */);
 
 /* ---- float32 instantiation of the boundary --------------------------------------------------------------
  * python/cutfemx/wrappers/fem.cpp:490-500 declares the runtime assembly for <T, U> in {float, double}^2 and

@@ -914,5 +914,39 @@ inline void extend_normal_velocity(const fem::FunctionSpace& V, const double* ph
 {
   check(cfx_extend_normal_velocity(V.handle.h, phi, interface_speed, speed, velocity, signed_distance, &options, device_info));
 }
+
+/// cfx_advect_options with the library's defaults (order 2, inside_tol 1e-12, no band, 4096 crossings; dt 0)
+struct AdvectOptions : cfx_advect_options
+{
+  AdvectOptions() { check(cfx_advect_options_default(this)); }
+};
+
+/// Move the P1 level set `phi` on `V` -- scalar, degree 1, on the geometry dofmap -- along the P1 velocity `velocity`
+/// ([nv * gdim], blocked: NormalExtensionResult::velocity as it stands) over the time `dt` by semi-Lagrangian
+/// characteristics, in place, in HBM (cfx_advect_level_set; the demo's _advect_level_set_characteristics).  The dt of
+/// `options` is replaced by the argument.  With options.max_distance = B > 0 the vertices with |phi| > B keep their
+/// value: the caller owes dt max|velocity| < B.  Only bad arguments throw; what became of the vertices is in the info.
+inline cfx_advect_info advect(const fem::FunctionSpace& V, std::span<double> phi, std::span<const double> velocity, double dt,
+                              const cfx_advect_options& options = AdvectOptions())
+{
+  const std::int64_t nv = V.ndofs;
+  const int gdim = V.ndofs_cell - 1; // (a P1 space of simplices with gdim = tdim: the library checks the rest)
+  if (V.bs != 1 || (std::int64_t)phi.size() != nv || (std::int64_t)velocity.size() != nv * gdim)
+    throw std::invalid_argument("advect: one value of phi and gdim values of velocity per vertex of a scalar space");
+  cfx_advect_options o = options;
+  o.dt = dt;
+  cfx_advect_info info{};
+  check(cfx_advect_level_set(V.handle.h, phi.data(), velocity.data(), phi.data(), nullptr, &o, &info));
+  return info;
+}
+/// ... with raw pointers (host or device; `out` may be `phi`, `cells` may be nullptr) and the cfx_advect_info left in HBM
+/// (`device_info`, or nullptr): with device arrays the call makes no host round trip
+inline void advect(const fem::FunctionSpace& V, const double* phi, const double* velocity, double* out, std::int32_t* cells, double dt,
+                   const cfx_advect_options& options, cfx_advect_info* device_info)
+{
+  cfx_advect_options o = options;
+  o.dt = dt;
+  check(cfx_advect_level_set(V.handle.h, phi, velocity, out, cells, &o, device_info));
+}
 } // namespace distance
 } // namespace cutfemx_amd
