@@ -153,6 +153,7 @@ SYMBOLS = [
     "cfx_pattern_view_get", "cfx_pattern_reuse_stats", "cfx_pattern_destroy", "cfx_assemble_matrix", "cfx_assemble_matrix_zeroed", "cfx_assemble_vector", "cfx_assemble_scalar",
     "cfx_apply_lifting", "cfx_set_bc", "cfx_zero_rows", "cfx_csr_block_merge", "cfx_csr_permute", "cfx_tabulate_entity", "cfx_active_domain", "cfx_active_view", "cfx_deactivate_outside",
     "cfx_active_destroy", "cfx_csr_spmv", "cfx_cg_options_default", "cfx_cg_solve", "cfx_minres_options_default", "cfx_minres_solve",
+    "cfx_bicgstab_options_default", "cfx_bicgstab_solve",
     "cfx_reinit_options_default", "cfx_reinitialize", "cfx_extend_options_default", "cfx_extend_normal_velocity",
     "cfx_advect_options_default", "cfx_advect_level_set", "cfx_mesh_cell_neighbours",
     "cfx_dist_unique_id", "cfx_dist_comm_create", "cfx_dist_comm_create_host", "cfx_dist_comm_create_device", "cfx_dist_comm_info", "cfx_dist_comm_destroy",

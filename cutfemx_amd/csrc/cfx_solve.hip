@@ -1,5 +1,5 @@
-// cutfemx_amd: the solve of assembled CSR systems in HBM -- y = A x, Jacobi-preconditioned conjugate gradients and
-// diagonally preconditioned MINRES.
+// cutfemx_amd: the solve of assembled CSR systems in HBM -- y = A x, Jacobi-preconditioned conjugate gradients,
+// diagonally preconditioned MINRES and Jacobi-preconditioned BiCGStab.
 //
 // Replaces the host solve of the reference's demos (python/demo/demo_poisson.py:46-58, demo_moving_poisson.py:53-67:
 // PETSc KSP on the assembled matrix) for the symmetric positive definite systems cfx_assemble_matrix +
@@ -52,6 +52,27 @@
 // minres_normalise (z /= gamma1, once).  MinresRecord continues CgRecord: the scalars of the recurrence -- gamma_k,
 // gamma_{k+1}, c and s of the last two rotations, eta -- live in two slots, iteration `it` reads slot it & 1 and block 0
 // of minres_update writes slot (it + 1) & 1; delta goes from minres_lanczos to minres_update through delta[it & 1].
+//
+// BiCGStab (cfx_bicgstab_solve) replaces the spsolve of the reference's SUPG level-set step
+// (python/demo/demo_compliance_optimization.py:1302-1350) for NONSYMMETRIC matrices.  It obeys every rule above.
+// van der Vorst's recurrence, right-preconditioned with M = diag(a_ii) (the sign kept) or I, so that the recurrence
+// residual is the residual of the original system and the stopping rule is CG's:
+//   by list position: r (s overwrites it in the half step), rhat = r0, v = A phat, t = A shat, p, 1/diag
+//   by row: phat = M^-1 p, shat = M^-1 s (read through the column indices, 0 outside the list), x
+// One iteration = five launches (launch number 5 it + {0 .. 4}):
+//   bicg_spmv_v     v = A phat, partials of rhat.v = sigma                       (solve_spmv_kernel<kBicgV>)
+//   bicg_half       alpha = rho / sigma;  s = r - alpha v over r, shat = M^-1 s;  partials of s.s
+//   bicg_spmv_t     t = A shat, partials of t.t and t.s                          (solve_spmv_kernel<kBicgT>)
+//   bicg_update     |s| <= threshold: x += alpha phat, converged.  Else omega = t.s / t.t;  x += alpha phat + omega shat,
+//                   r = s - omega t;  partials of rhat.r and r.r
+//   bicg_direction  the stopping test;  beta = (rho' / rho)(alpha / omega);  p = r + beta (p - omega v), phat = M^-1 p
+// (|s| is known to every block only one launch after the half step, so bicg_spmv_t runs before the half-step test is
+// taken: on the converging iteration its product is not used.)  Set-up: bicg_init (solve_spmv_kernel<kBicgInit>: kInit's
+// row pass, which also stores rhat = p = r0) and bicg_start (one block; rho_0 = r0.r0).  BicgRecord continues CgRecord:
+// rho of iteration it in rho[it & 1] (bicg_direction writes [(it + 1) & 1]), alpha[it & 1] from bicg_half to bicg_update
+// and bicg_direction, omega[it & 1] from bicg_update to bicg_direction.  Five slabs: sigma | s.s | t.t | t.s | rhat.r, r.r
+// share none that one launch both reads and writes.  Workspace: r, rhat, v, t, p, 1/diag = 48 B per iterated row, phat and
+// shat = 16 B per matrix row, the slabs (80 KB), the record.
 #include "cfx_device.h"
 
 using namespace cfx;
@@ -60,7 +81,7 @@ namespace
 {
 constexpr int kMaxGrid = 2048; // blocks of every solve kernel (8 waves per SIMD on 256 CUs); slabs of 16 KB
 constexpr int kRunning = 0;    // state word; every other value is the cfx_cg_info::reason
-enum { kPlain = 0, kInit = 1, kCg = 2, kMinresInit = 3 };
+enum { kPlain = 0, kInit = 1, kCg = 2, kMinresInit = 3, kBicgInit = 4, kBicgV = 5, kBicgT = 6 };
 
 struct CgRecord
 {
@@ -85,6 +106,12 @@ struct MinresRecord : CgRecord // (the kernels shared with CG see the CgRecord)
 {
   MinresScalars sc[2]; // iteration it reads [it & 1]; block 0 of minres_update writes [(it + 1) & 1]
   double delta[2];     // z.Az of iteration it in [it & 1]: minres_lanczos -> minres_update
+};
+
+struct BicgRecord : CgRecord // (the kernels shared with CG see the CgRecord)
+{
+  double alpha[2]; // of iteration it in [it & 1]: bicg_half -> bicg_update, bicg_direction
+  double omega[2]; // of iteration it in [it & 1]: bicg_update -> bicg_direction
 };
 
 struct SolveArgs
@@ -119,6 +146,14 @@ struct SolveArgs
   int it;              // iteration (0-based)
   int launch;          // 3 it + {0, 1, 2}
   int last;            // it + 1 == max_iter
+  // BiCGStab (r, rhat, q = v, t, pl = p, dinv by list position; p = phat, shat by row); launch = 5 it + {0 .. 4}
+  double* rhat;
+  double* t;
+  double* pl;
+  double* shat;
+  double* slab3;       // partials: slab0 rhat.v and t.t, slab1 s.s, slab2 t.s, slab3 rhat.r, slab4 r.r
+  double* slab4;
+  BicgRecord* brec;    // == rec
 };
 
 __host__ __device__ inline int lanes_for(int64_t nnz, int64_t n)
@@ -158,7 +193,8 @@ __device__ __forceinline__ int state_in(const SolveArgs& S)
   return st;
 }
 
-// The rows of this block's tiles, L lanes each.  acc: the thread's running sums (kInit: r.z, r.r, b.b; kCg: p.q).
+// The rows of this block's tiles, L lanes each.  acc: the thread's running sums (kInit: r.z, r.r, b.b; kCg: p.q;
+// kBicgV: rhat.v; kBicgT: t.t, t.s).
 // A row costs a chain of dependent loads (rows[k] -> indptr[row] -> indices[j] -> x[c]), so kTiles tiles of the block's
 // sequence are walked side by side: their loads are in flight together.  The order of every sum is that of one tile
 // after the other -- a lane adds its entries of a row in ascending order, the thread adds tile t before tile t + grid.
@@ -226,7 +262,7 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
         if (j[u] < j1[u])
         {
           s[u] += v[u] * xv[u];
-          if (MODE == kInit && c[u] == row[u]) d[u] += v[u];
+          if ((MODE == kInit || MODE == kBicgInit) && c[u] == row[u]) d[u] += v[u];
           if (MODE == kMinresInit)
           {
             if (S.pc == CFX_PC_ABS_ROWSUM)
@@ -246,7 +282,7 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
       for (int o = L / 2; o > 0; o >>= 1)
       {
         s[u] += __shfl_down(s[u], o, L);
-        if (MODE == kInit || MODE == kMinresInit) d[u] += __shfl_down(d[u], o, L);
+        if (MODE == kInit || MODE == kMinresInit || MODE == kBicgInit) d[u] += __shfl_down(d[u], o, L);
       }
     }
 #pragma unroll
@@ -259,6 +295,17 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
       {
         S.q[k[u]] = s[u];
         acc[0] += S.x[row[u]] * s[u];
+      }
+      else if (MODE == kBicgV)
+      {
+        S.q[k[u]] = s[u];
+        acc[0] += S.rhat[k[u]] * s[u];
+      }
+      else if (MODE == kBicgT)
+      {
+        S.t[k[u]] = s[u];
+        acc[0] += s[u] * s[u];
+        acc[1] += s[u] * S.r[k[u]];
       }
       else if (MODE == kMinresInit)
       {
@@ -293,6 +340,7 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
         }
         S.r[k[u]] = rk;
         S.p[row[u]] = z;
+        if (MODE == kBicgInit) S.rhat[k[u]] = S.pl[k[u]] = rk;
         acc[0] += rk * z;
         acc[1] += rk * rk;
         acc[2] += bk * bk;
@@ -303,12 +351,13 @@ __device__ __forceinline__ void spmv_rows(const SolveArgs& S, double* acc)
 
 // kPlain: y[rows] = (A x)[rows].  kInit: r = b - A x0, 1/diag, z = r / diag, p = z, partials of r.z, r.r, b.b.
 // kCg: q = A p, partials of p.q.  kMinresInit: r0 = b - A x0 into v, 1/m, z = M^-1 r0 into p, v_old = w = w_old = 0,
-// partials of r0 . M^-1 r0 and b . M^-1 b.
+// partials of r0 . M^-1 r0 and b . M^-1 b.  kBicgInit: kInit, and rhat = p = r by list position.  kBicgV: q = A phat,
+// partials of rhat.q.  kBicgT: t = A shat, partials of t.t (slab0) and t.s (slab2; s lives in r).
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) solve_spmv_kernel(SolveArgs S)
 {
   __shared__ double wave_sums[kBlock / 64];
-  if (MODE == kCg && state_in(S) != kRunning) return;
+  if ((MODE == kCg || MODE == kBicgV || MODE == kBicgT) && state_in(S) != kRunning) return;
   const int L = S.lanes ? S.lanes : lanes_for((int64_t)S.rec->nnz, S.n);
   double acc[3] = {0.0, 0.0, 0.0};
   switch (L) // (uniform in the launch)
@@ -327,7 +376,12 @@ __global__ void __launch_bounds__(kBlock) solve_spmv_kernel(SolveArgs S)
     const double s1 = block_sum_all(acc[1], wave_sums);
     if (threadIdx.x == 0) S.slab1[blockIdx.x] = s1;
   }
-  if (MODE == kInit)
+  if (MODE == kBicgT)
+  {
+    const double s1 = block_sum_all(acc[1], wave_sums);
+    if (threadIdx.x == 0) S.slab2[blockIdx.x] = s1; // (slab1 holds s.s, which bicg_update reads)
+  }
+  if (MODE == kInit || MODE == kBicgInit)
   {
     const double s1 = block_sum_all(acc[1], wave_sums), s2 = block_sum_all(acc[2], wave_sums);
     if (threadIdx.x == 0)
@@ -601,6 +655,153 @@ __global__ void __launch_bounds__(kBlock) minres_update_kernel(SolveArgs S)
   }
 }
 
+// ---- BiCGStab -------------------------------------------------------------------------------------------------------
+// ONE block, after bicg_init: the norms, the threshold, rho of iteration 0 (rhat.r = r0.r0) and the state the first
+// launch reads
+__global__ void __launch_bounds__(kBlock) bicg_start_kernel(SolveArgs S, double rtol, double atol, int max_iter)
+{
+  __shared__ double wave_sums[kBlock / 64];
+  const double rr = slab_sum(S.slab1, S.nslab, wave_sums), bb = slab_sum(S.slab2, S.nslab, wave_sums);
+  if (threadIdx.x != 0) return;
+  CgRecord& R = *S.rec;
+  const double bnorm = sqrt(bb), rnorm = sqrt(rr), threshold = fmax(rtol * bnorm, atol);
+  int st = kRunning;
+  if (S.dinv && R.bad_diagonal)
+    st = CFX_CG_BAD_DIAGONAL;
+  else if (rnorm <= threshold)
+    st = CFX_CG_CONVERGED;
+  else if (max_iter == 0)
+    st = CFX_CG_MAX_ITER;
+  R.info.reason = st;
+  R.info.iterations = 0;
+  R.info.residual_norm = rnorm;
+  R.info.rhs_norm = bnorm;
+  R.threshold = threshold;
+  R.rho[0] = rr;
+  R.state[0] = st;
+}
+
+// sigma = rhat.v;  alpha = rho / sigma;  s = r - alpha v over r, shat = M^-1 s;  partials of s.s
+__global__ void __launch_bounds__(kBlock) bicg_half_kernel(SolveArgs S)
+{
+  __shared__ double wave_sums[kBlock / 64];
+  if (state_in(S) != kRunning) return;
+  const double sigma = slab_sum(S.slab0, S.nslab, wave_sums);
+  const bool breakdown = sigma == 0.0 || !isfinite(sigma); // (x is the iterate before)
+  const double alpha = S.brec->rho[S.it & 1] / sigma;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    S.brec->state[(S.launch + 1) & 1] = breakdown ? CFX_CG_BREAKDOWN : kRunning;
+    if (breakdown) S.brec->info.reason = CFX_CG_BREAKDOWN;
+    S.brec->alpha[S.it & 1] = alpha;
+  }
+  if (breakdown) return;
+  double ss = 0.0;
+  const int64_t tiles = (S.n + kBlock - 1) / kBlock;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x)
+  {
+    const int64_t k = t * kBlock + threadIdx.x;
+    if (k < S.n)
+    {
+      const int64_t row = S.rows ? (int64_t)S.rows[k] : k;
+      const double sk = S.r[k] - alpha * S.q[k];
+      S.r[k] = sk;
+      S.shat[row] = S.dinv ? sk * S.dinv[k] : sk;
+      ss += sk * sk;
+    }
+  }
+  const double s0 = block_sum_all(ss, wave_sums);
+  if (threadIdx.x == 0) S.slab1[blockIdx.x] = s0; // (slab0 holds rhat.v, which other blocks of this launch may still be reading)
+}
+
+// |s| <= threshold: x += alpha phat and the solve has converged.  Else omega = t.s / t.t;  x += alpha phat + omega shat,
+// r = s - omega t;  partials of rhat.r and r.r.  (s.s comes from bicg_half, whose grid is this launch's.)
+__global__ void __launch_bounds__(kBlock) bicg_update_kernel(SolveArgs S)
+{
+  __shared__ double wave_sums[kBlock / 64];
+  if (state_in(S) != kRunning) return;
+  const double ss = slab_sum(S.slab1, gridDim.x, wave_sums), tt = slab_sum(S.slab0, S.nslab, wave_sums),
+               ts = slab_sum(S.slab2, S.nslab, wave_sums);
+  BicgRecord& R = *S.brec;
+  const double snorm = sqrt(ss), alpha = R.alpha[S.it & 1];
+  const bool half = snorm <= R.threshold;
+  const bool breakdown = !half && (!isfinite(tt) || !(tt > 0.0) || !isfinite(ts)); // (no update of x)
+  const double omega = half ? 0.0 : ts / tt;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    if (half)
+    {
+      R.info.iterations = S.it + 1;
+      R.info.residual_norm = snorm;
+    }
+    if (half || breakdown) R.info.reason = half ? CFX_CG_CONVERGED : CFX_CG_BREAKDOWN;
+    R.state[(S.launch + 1) & 1] = half ? CFX_CG_CONVERGED : (breakdown ? CFX_CG_BREAKDOWN : kRunning);
+    R.omega[S.it & 1] = omega;
+  }
+  if (breakdown) return;
+  double hr = 0.0, rr = 0.0;
+  const int64_t tiles = (S.n + kBlock - 1) / kBlock;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x)
+  {
+    const int64_t k = t * kBlock + threadIdx.x;
+    if (k < S.n)
+    {
+      const int64_t row = S.rows ? (int64_t)S.rows[k] : k;
+      if (half)
+        S.xs[row] += alpha * S.p[row];
+      else
+      {
+        S.xs[row] += alpha * S.p[row] + omega * S.shat[row];
+        const double rk = S.r[k] - omega * S.t[k];
+        S.r[k] = rk;
+        hr += S.rhat[k] * rk;
+        rr += rk * rk;
+      }
+    }
+  }
+  if (half) return; // (uniform in the launch)
+  const double s0 = block_sum_all(hr, wave_sums), s1 = block_sum_all(rr, wave_sums);
+  if (threadIdx.x == 0)
+  {
+    S.slab3[blockIdx.x] = s0; // (slabs 0 .. 2 are being read by other blocks of this launch)
+    S.slab4[blockIdx.x] = s1;
+  }
+}
+
+// the stopping test, then beta = (rho' / rho)(alpha / omega);  p = r + beta (p - omega v), phat = M^-1 p
+__global__ void __launch_bounds__(kBlock) bicg_direction_kernel(SolveArgs S)
+{
+  __shared__ double wave_sums[kBlock / 64];
+  if (state_in(S) != kRunning) return;
+  const double rho1 = slab_sum(S.slab3, S.nslab, wave_sums), rr = slab_sum(S.slab4, S.nslab, wave_sums);
+  BicgRecord& R = *S.brec;
+  const double rnorm = sqrt(rr), omega = R.omega[S.it & 1];
+  const bool stuck = omega == 0.0 || !isfinite(omega) || rho1 == 0.0 || !isfinite(rho1); // (x is this iterate)
+  const int st = rnorm <= R.threshold ? CFX_CG_CONVERGED : S.last ? CFX_CG_MAX_ITER : stuck ? CFX_CG_BREAKDOWN : kRunning;
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+  {
+    R.rho[(S.it + 1) & 1] = rho1;
+    R.info.iterations = S.it + 1;
+    R.info.residual_norm = rnorm;
+    if (st != kRunning) R.info.reason = st;
+    R.state[(S.launch + 1) & 1] = st;
+  }
+  if (st != kRunning) return;
+  const double beta = (rho1 / R.rho[S.it & 1]) * (R.alpha[S.it & 1] / omega);
+  const int64_t tiles = (S.n + kBlock - 1) / kBlock;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x)
+  {
+    const int64_t k = t * kBlock + threadIdx.x;
+    if (k < S.n)
+    {
+      const int64_t row = S.rows ? (int64_t)S.rows[k] : k;
+      const double pk = S.r[k] + beta * (S.pl[k] - omega * S.q[k]);
+      S.pl[k] = pk;
+      S.p[row] = S.dinv ? pk * S.dinv[k] : pk;
+    }
+  }
+}
+
 bool lanes_ok(int l) { return l == 0 || l == 1 || l == 4 || l == 8 || l == 16 || l == 64; }
 
 // blocks of a kernel over n items, `per` a block tile: at least one (every slab is written), at most kMaxGrid
@@ -827,6 +1028,101 @@ int cfx_minres_solve(int64_t nrows, const int64_t* indptr, const int32_t* indice
     S.launch = 3 * it + 3;
     S.nslab = g_vec;
     launch("minres_update", minres_update_kernel, dim3(g_vec), dim3(kBlock), 0, S);
+    // the host looks every check_every iterations; what it sees only ends the launches (the result is frozen in HBM)
+    if (o.check_every > 0 && (it + 1) % o.check_every == 0 && !S.last && read_scalar(&rec.p->info.reason) != kRunning) break;
+  }
+  if (is_device_pointer(info))
+    CFX_HIP(hipMemcpyAsync(info, &rec.p->info, sizeof(cfx_cg_info), hipMemcpyDeviceToDevice, ctx().stream));
+  else
+    *info = read_scalar(&rec.p->info);
+  xo.finish();
+  CFX_API_END
+}
+
+int cfx_bicgstab_options_default(cfx_bicgstab_options* opt)
+{
+  CFX_API_BEGIN
+  require(opt != nullptr, CFX_ERR_INVALID_ARGUMENT, "cfx_bicgstab_options_default: null argument");
+  opt->rtol = 1e-10;
+  opt->atol = 0.0;
+  opt->max_iter = 10000;
+  opt->check_every = 16;
+  opt->precond = CFX_PC_JACOBI;
+  opt->lanes_per_row = 0;
+  CFX_API_END
+}
+
+int cfx_bicgstab_solve(int64_t nrows, const int64_t* indptr, const int32_t* indices, const double* values, const int32_t* rows,
+                       int64_t n_rows, const double* b, double* x, const cfx_bicgstab_options* opt, cfx_cg_info* info)
+{
+  CFX_API_BEGIN
+  cfx_bicgstab_options o;
+  if (opt)
+    o = *opt;
+  else
+    cfx_bicgstab_options_default(&o);
+  check_csr("cfx_bicgstab_solve", nrows, indptr, indices, values, rows, n_rows, o.lanes_per_row);
+  require(b && x && info, CFX_ERR_INVALID_ARGUMENT, "cfx_bicgstab_solve: null b, x or info");
+  require(o.rtol >= 0.0 && o.atol >= 0.0, CFX_ERR_INVALID_ARGUMENT, "cfx_bicgstab_solve: rtol and atol are >= 0");
+  require(o.max_iter >= 0 && o.check_every >= 0, CFX_ERR_INVALID_ARGUMENT, "cfx_bicgstab_solve: max_iter and check_every are >= 0");
+  require(o.max_iter <= 0x19999999, CFX_ERR_INVALID_ARGUMENT, "cfx_bicgstab_solve: max_iter too large"); // (5 launches each)
+  require(o.precond == CFX_PC_NONE || o.precond == CFX_PC_JACOBI, CFX_ERR_INVALID_ARGUMENT,
+          "cfx_bicgstab_solve: precond is CFX_PC_NONE or CFX_PC_JACOBI");
+  ctx().ensure();
+  for (const void* p : {(const void*)indptr, (const void*)indices, (const void*)values})
+    require_device("cfx_bicgstab_solve", p, "the CSR arrays");
+  if (rows) require_device("cfx_bicgstab_solve", rows, "rows");
+
+  const int64_t n = rows ? n_rows : nrows;
+  const bool pc = o.precond == CFX_PC_JACOBI;
+  DevArray<double> bd = to_device(b, nrows);
+  OutArray<double> xo(x, nrows, true);
+  // workspace from the block cache: r, rhat, v, t, p, 1/diag by list position, phat, shat by row, five slabs, the record
+  DevArray<double> r(n), rhat(n), v(n), t(n), pl(n), dinv(pc ? n : 0), phat(nrows), shat(nrows), slabs(5 * (int64_t)kMaxGrid);
+  DevArray<BicgRecord> rec(1);
+  rec.zero();
+  if (rows) // phat and shat stay 0 outside the list
+  {
+    phat.zero();
+    shat.zero();
+  }
+
+  SolveArgs S{};
+  S.indptr = indptr; S.indices = indices; S.values = values; S.rows = rows;
+  S.n = n;
+  S.lanes = o.lanes_per_row;
+  S.rec = rec.p; S.brec = rec.p;
+  S.b = bd.p; S.xs = xo.dev; S.r = r.p; S.rhat = rhat.p; S.q = v.p; S.t = t.p; S.pl = pl.p; S.p = phat.p; S.shat = shat.p;
+  S.dinv = pc ? dinv.p : nullptr;
+  S.slab0 = slabs.p; S.slab1 = slabs.p + kMaxGrid; S.slab2 = slabs.p + 2 * kMaxGrid;
+  S.slab3 = slabs.p + 3 * kMaxGrid; S.slab4 = slabs.p + 4 * kMaxGrid;
+  if (S.lanes == 0) count_entries(S, nrows);
+
+  const int g_rows = spmv_blocks(n), g_vec = grid_blocks(n, kBlock);
+  S.x = xo.dev;
+  launch("bicg_init", solve_spmv_kernel<kBicgInit>, dim3(g_rows), dim3(kBlock), 0, S);
+  S.nslab = g_rows;
+  launch("bicg_start", bicg_start_kernel, dim3(1), dim3(kBlock), 0, S, o.rtol, o.atol, (int)o.max_iter);
+
+  for (int it = 0; it < o.max_iter; ++it)
+  {
+    S.it = it;
+    S.last = it + 1 == o.max_iter;
+    S.launch = 5 * it;
+    S.x = phat.p;
+    launch("bicg_spmv_v", solve_spmv_kernel<kBicgV>, dim3(g_rows), dim3(kBlock), 0, S);
+    S.launch = 5 * it + 1;
+    S.nslab = g_rows;
+    launch("bicg_half", bicg_half_kernel, dim3(g_vec), dim3(kBlock), 0, S);
+    S.launch = 5 * it + 2;
+    S.x = shat.p;
+    launch("bicg_spmv_t", solve_spmv_kernel<kBicgT>, dim3(g_rows), dim3(kBlock), 0, S);
+    S.launch = 5 * it + 3;
+    S.nslab = g_rows; // (t.t and t.s; s.s has one partial per block of bicg_half)
+    launch("bicg_update", bicg_update_kernel, dim3(g_vec), dim3(kBlock), 0, S);
+    S.launch = 5 * it + 4;
+    S.nslab = g_vec;
+    launch("bicg_direction", bicg_direction_kernel, dim3(g_vec), dim3(kBlock), 0, S);
     // the host looks every check_every iterations; what it sees only ends the launches (the result is frozen in HBM)
     if (o.check_every > 0 && (it + 1) % o.check_every == 0 && !S.last && read_scalar(&rec.p->info.reason) != kRunning) break;
   }

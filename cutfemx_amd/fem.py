@@ -995,6 +995,32 @@ def minres_solve(A, b, x0=None, *, rtol: float = 1e-10, atol: float = 0.0, max_i
     return _krylov_solve("minres_solve", "cfx_minres_solve", o, A, b, x0, rows, domain, info_out)
 
 
+def bicgstab_default_options() -> _lib.CGOptions:
+    """The defaults of cfx_bicgstab_options_default (no GPU needed)."""
+    o = _lib.CGOptions()
+    _lib.check(_lib.load().cfx_bicgstab_options_default(C.byref(o)))
+    return o
+
+
+def bicgstab_solve(A, b, x0=None, *, rtol: float = 1e-10, atol: float = 0.0, max_iter: int | None = None,
+                   precond: str | None = "jacobi", rows=None, domain=None, check_every: int | None = None, info_out=None,
+                   lanes_per_row: int = 0):
+    """Solve A x = b for a NONSYMMETRIC A by right-preconditioned BiCGStab in HBM (cfx_bicgstab_solve); returns
+    (x, info) -- what python/demo/demo_compliance_optimization.py:1302-1350 leaves to spsolve.
+
+    Arguments, row-list semantics and return value are those of cg_solve (`A`: MatrixCSR, MergedCSR or csr_from_arrays);
+    the matrix need be neither symmetric nor definite.  precond: "jacobi" (d_i = a_ii with its sign; a listed row without
+    a nonzero stored diagonal gives reason CG_BAD_DIAGONAL) or None / "none".  The preconditioner acts from the right, so
+    the rule is cg_solve's: |r|_2 <= max(rtol |b|_2, atol) with r the residual of the system itself; info.residual_norm /
+    rhs_norm are these 2-norms.  CG_BREAKDOWN: a scalar of the recurrence vanished or is not finite (the header lists
+    which iterate x then holds)."""
+    _csr_arrays(A)
+    o = _krylov_options("bicgstab_solve", bicgstab_default_options(), A, rows, domain,
+                        {"jacobi": PC_JACOBI, "none": PC_NONE, None: PC_NONE}, precond, rtol, atol, max_iter, check_every,
+                        lanes_per_row)
+    return _krylov_solve("bicgstab_solve", "cfx_bicgstab_solve", o, A, b, x0, rows, domain, info_out)
+
+
 def zero_rows(A: MatrixCSR, *, tol: float = 0.0) -> np.ndarray:
     """Rows whose assembled entries are all <= tol in magnitude (python/cutfemx/fem.py:777-782)."""
     p, n = C.c_void_p(), C.c_int64()

@@ -754,6 +754,44 @@ int cfx_minres_solve(int64_t nrows, const int64_t* indptr, const int32_t* indice
                      const int32_t* rows, int64_t n_rows, const double* b, double* x /* in: x0, out: x */,
                      const cfx_minres_options* opt /* or NULL: the defaults */, cfx_cg_info* info /* host or device pointer */);
 
+/* ---- the solve of NONSYMMETRIC systems: Jacobi-preconditioned BiCGStab ---------------------------------------------
+ * What the reference's shape-optimisation demo hands to spsolve in its SUPG level-set step
+ * (python/demo/demo_compliance_optimization.py:1302-1350), and any convection-diffusion or nonsymmetric Nitsche system:
+ * a square float64 CSR matrix that need be neither symmetric nor definite, solved in HBM.
+ *
+ * The arguments, the row list (entries of x outside the list are never written and act as data), lanes_per_row,
+ * check_every (0: exactly max_iter iterations are launched; with a device `info` no host round trip), the host / device
+ * rules for b, x and info, and the fixed order of every sum are those of cfx_cg_solve; cfx_cg_info and the CFX_CG_*
+ * reasons are reused, and every reason returns status 0.  Preconditioners: CFX_PC_NONE (M = I) and CFX_PC_JACOBI
+ * (M = diag(d), d_i = a_ii WITH its sign; a listed row without a stored diagonal entry, or with a zero one, gives
+ * CFX_CG_BAD_DIAGONAL and x = x0).  CFX_PC_ABS_JACOBI and CFX_PC_ABS_ROWSUM are refused.
+ *
+ * The preconditioner acts from the RIGHT, so the recurrence residual is the residual of the original system and the
+ * stopping rule is cfx_cg_solve's: |r|_2 <= threshold = max(rtol |b|_2, atol), both norms over the iterated rows.
+ *   r = b - A x0 (iterated rows);  rhat = r;  rho = rhat.r;  p = r
+ *   0 iterations: BAD_DIAGONAL, else CONVERGED if |r| <= threshold, else MAX_ITER if max_iter == 0
+ *   iteration it:
+ *     phat = M^-1 p;  v = A phat;  sigma = rhat.v
+ *         sigma == 0 or not finite            -> BREAKDOWN, iterations = it, x unchanged
+ *     alpha = rho / sigma;  s = r - alpha v
+ *         |s| <= threshold                    -> x += alpha phat; CONVERGED, iterations = it + 1, residual_norm = |s|
+ *     shat = M^-1 s;  t = A shat;  tt = t.t;  ts = t.s
+ *         tt not finite or not > 0, or ts not finite -> BREAKDOWN, iterations = it, x unchanged
+ *     omega = ts / tt;  x += alpha phat + omega shat;  r = s - omega t;  rho' = rhat.r
+ *         |r| <= threshold                    -> CONVERGED, it + 1
+ *         it + 1 == max_iter                  -> MAX_ITER, it + 1
+ *         omega or rho' zero or not finite    -> BREAKDOWN, it + 1 (x is this iterate)
+ *     beta = (rho' / rho)(alpha / omega);  p = r + beta (p - omega v);  rho = rho'
+ * phat and shat are indexed by row and stay 0 outside the list, so columns outside the list enter r0 = b - A x0 and
+ * nothing else: the call solves A[rows, rows] x[rows] = b[rows] - A[rows, others] x[others].  residual_norm is |r|_2 of
+ * the recurrence at the iterate x holds. */
+typedef cfx_cg_options cfx_bicgstab_options;
+int cfx_bicgstab_options_default(cfx_bicgstab_options* opt); /* rtol 1e-10, atol 0, max_iter 10000, check_every 16,
+                                                                CFX_PC_JACOBI, lanes 0; works without a GPU */
+int cfx_bicgstab_solve(int64_t nrows, const int64_t* indptr, const int32_t* indices, const double* values,
+                       const int32_t* rows, int64_t n_rows, const double* b, double* x /* in: x0, out: x */,
+                       const cfx_bicgstab_options* opt /* or NULL: the defaults */, cfx_cg_info* info /* host or device pointer */);
+
 /* ---- reinitialisation: a P1 level set back to a signed distance function, in HBM ----------------------------------
  * cutfemx.distance.reinitialize(phi, max_iter, tol) of the reference (cpp/cutfemx/distance/reinitialize.h:490-575,
  * fast_iterative.h:146-468, eikonal_update.h; python/cutfemx/distance.py:154-160): the stage a moving-domain loop runs

@@ -685,6 +685,37 @@ inline void minres_solve(const SparsityPattern& pattern, const double* values, c
                          device_info));
 }
 
+/// cfx_bicgstab_options with the library's defaults (rtol 1e-10, Jacobi, check_every 16 ...)
+struct BicgstabOptions : cfx_bicgstab_options
+{
+  BicgstabOptions() { check(cfx_bicgstab_options_default(this)); }
+};
+
+/// Right-preconditioned (Jacobi) BiCGStab in HBM (cfx_bicgstab_solve) on a NONSYMMETRIC system -- the SUPG level-set
+/// step, convection-diffusion on a cut domain: replaces the spsolve of
+/// python/demo/demo_compliance_optimization.py:1302-1350.  Arguments, reasons and the stopping rule
+/// (|r|_2 <= max(rtol |b|_2, atol), r the residual of the system itself) as for cg_solve.
+inline cfx_cg_info bicgstab_solve(const SparsityPattern& pattern, const double* values, std::span<const double> b,
+                                  std::span<double> x, const cfx_bicgstab_options& options = BicgstabOptions(),
+                                  const std::int32_t* rows = nullptr, std::int64_t n_rows = 0)
+{
+  if ((std::int64_t)b.size() != pattern.view.nrows || x.size() != b.size() || pattern.view.ncols != pattern.view.nrows)
+    throw std::invalid_argument("bicgstab_solve: a square matrix and one entry of b and x per row");
+  cfx_cg_info info{};
+  check(cfx_bicgstab_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b.data(),
+                           x.data(), &options, &info));
+  return info;
+}
+/// ... with the cfx_cg_info left in HBM (`device_info`): with device `b` / `x` and options.check_every = 0 the call
+/// makes no host round trip
+inline void bicgstab_solve(const SparsityPattern& pattern, const double* values, const double* b, double* x,
+                           const cfx_bicgstab_options& options, cfx_cg_info* device_info, const std::int32_t* rows = nullptr,
+                           std::int64_t n_rows = 0)
+{
+  check(cfx_bicgstab_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b, x, &options,
+                           device_info));
+}
+
 /// One block of a MatrixCSR block system: the values of A[i][j] with their pattern (nullptr: an absent block)
 struct MatrixBlock
 {
