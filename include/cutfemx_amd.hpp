@@ -629,6 +629,23 @@ inline void spmv(const SparsityPattern& pattern, const double* values, const dou
   check(cfx_csr_spmv(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, lanes_per_row, x, y));
 }
 
+namespace solve_detail
+{
+/// What the host-info overloads of the three solvers share: the size check, the call of `entry` (cfx_cg_solve,
+/// cfx_minres_solve and cfx_bicgstab_solve have one argument list), the info.
+inline cfx_cg_info krylov_solve(const char* who, decltype(&cfx_cg_solve) entry, const SparsityPattern& pattern,
+                                const double* values, std::span<const double> b, std::span<double> x,
+                                const cfx_cg_options& options, const std::int32_t* rows, std::int64_t n_rows)
+{
+  if ((std::int64_t)b.size() != pattern.view.nrows || x.size() != b.size() || pattern.view.ncols != pattern.view.nrows)
+    throw std::invalid_argument(std::string(who) + ": a square matrix and one entry of b and x per row");
+  cfx_cg_info info{};
+  check(entry(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b.data(), x.data(), &options,
+              &info));
+  return info;
+}
+} // namespace solve_detail
+
 /// Jacobi-preconditioned conjugate gradients in HBM (cfx_cg_solve) on the symmetric positive definite system a
 /// deactivated cut problem gives: replaces the PETSc KSP of python/demo/demo_poisson.py:46-58.  `values` (and `rows`, the
 /// optional list of iterated rows) are device pointers; `b` and `x` (start vector in, solution out) host or device.
@@ -637,12 +654,7 @@ inline cfx_cg_info cg_solve(const SparsityPattern& pattern, const double* values
                             std::span<double> x, const cfx_cg_options& options = CGOptions(),
                             const std::int32_t* rows = nullptr, std::int64_t n_rows = 0)
 {
-  if ((std::int64_t)b.size() != pattern.view.nrows || x.size() != b.size() || pattern.view.ncols != pattern.view.nrows)
-    throw std::invalid_argument("cg_solve: a square matrix and one entry of b and x per row");
-  cfx_cg_info info{};
-  check(cfx_cg_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b.data(), x.data(),
-                     &options, &info));
-  return info;
+  return solve_detail::krylov_solve("cg_solve", cfx_cg_solve, pattern, values, b, x, options, rows, n_rows);
 }
 /// ... with the cfx_cg_info left in HBM (`device_info`): with device `b` / `x` and options.check_every = 0 the call
 /// makes no host round trip
@@ -668,12 +680,7 @@ inline cfx_cg_info minres_solve(const SparsityPattern& pattern, const double* va
                                 std::span<double> x, const cfx_minres_options& options = MinresOptions(),
                                 const std::int32_t* rows = nullptr, std::int64_t n_rows = 0)
 {
-  if ((std::int64_t)b.size() != pattern.view.nrows || x.size() != b.size() || pattern.view.ncols != pattern.view.nrows)
-    throw std::invalid_argument("minres_solve: a square matrix and one entry of b and x per row");
-  cfx_cg_info info{};
-  check(cfx_minres_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b.data(),
-                         x.data(), &options, &info));
-  return info;
+  return solve_detail::krylov_solve("minres_solve", cfx_minres_solve, pattern, values, b, x, options, rows, n_rows);
 }
 /// ... with the cfx_cg_info left in HBM (`device_info`): with device `b` / `x` and options.check_every = 0 the call
 /// makes no host round trip
@@ -699,12 +706,7 @@ inline cfx_cg_info bicgstab_solve(const SparsityPattern& pattern, const double* 
                                   std::span<double> x, const cfx_bicgstab_options& options = BicgstabOptions(),
                                   const std::int32_t* rows = nullptr, std::int64_t n_rows = 0)
 {
-  if ((std::int64_t)b.size() != pattern.view.nrows || x.size() != b.size() || pattern.view.ncols != pattern.view.nrows)
-    throw std::invalid_argument("bicgstab_solve: a square matrix and one entry of b and x per row");
-  cfx_cg_info info{};
-  check(cfx_bicgstab_solve(pattern.view.nrows, pattern.view.indptr, pattern.view.indices, values, rows, n_rows, b.data(),
-                           x.data(), &options, &info));
-  return info;
+  return solve_detail::krylov_solve("bicgstab_solve", cfx_bicgstab_solve, pattern, values, b, x, options, rows, n_rows);
 }
 /// ... with the cfx_cg_info left in HBM (`device_info`): with device `b` / `x` and options.check_every = 0 the call
 /// makes no host round trip
