@@ -13,6 +13,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -164,6 +165,14 @@ inline dim3 grid_for(int64_t n, int block = 256)
   return dim3((unsigned)g);
 }
 
+// f(std::integral_constant<int, tdim>{}) for the two mesh dimensions: picks the <2> or <3> instance of a kernel
+template <class F>
+inline void for_tdim(int tdim, F&& f)
+{
+  if (tdim == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 3>{});
+}
+
 // ---------------------------------------------------------------------------
 // HBM block cache.  All work is issued in order on one stream, so a block
 // released on the host can be handed to a later launch without an event.
@@ -255,7 +264,7 @@ struct Count
 // what a site hands to publish: where queued work leaves the total, and how to read it
 enum CountKind { kCountI64 = 0, kCountI32 = 1, kCountPackedLo = 2, kCountPackedHi = 3,
                  kCountLo32 = 4, kCountHi32 = 5, kCountSum32 = 6 }; // halves of an int64 of two packed 32-bit totals, their sum
-constexpr int kCountPackShift = 34; // packed totals: low bits | high bits << kCountPackShift (the rule scans of cfx_cut.hip)
+constexpr int kCountPackShift = 34; // packed totals: low bits | high bits << kCountPackShift (the rule scans of cfx_rules.hip)
 // how a site's capacity follows from its value in the previous step: a length that may grow (x margin + slack), or a
 // quantity the host branches on (a flag word, a size class) that has to come out EQUAL or the step is void
 // kCountSizeClass: a maximum the host only compares with 32 / 64 / 128 / 256 (row-length classes that select kernel
